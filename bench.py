@@ -19,6 +19,11 @@ N > 1: ONE genome sharded across the ranks ("scaling": "strong"): reads by pile,
 all-to-alls + one all-reduce per flush window (raven_amd/sharded.py), polishing windows sharded by range.
 
 Prints ONE JSON line on rank 0 (metric contract + "roofline" + "cpu_baseline").
+A plain run sets up, warms up, times the steps and prints the line; "roofline", "kernels" and "cpu_baseline" are null
+in it.  --full adds what takes work of its own: per-kernel HIP events inside the timed steps (kernels, roofline), the
+overlap pass through the host boundary, the input path on a gz FASTQ and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's share at N > 1) as DIR/<name>.npy: see
+dump_outputs().
 """
 import argparse
 import json
@@ -182,6 +187,61 @@ def cpu_baseline(args, cores):
             "kind": "port", "sample": sample}
 
 
+DUMP_ROWS = 1 << 17  # rows of a sampled overlap table (8 float64 columns: 8.4 MB)
+DUMP_VALUES = 1 << 19  # float64 values of a sampled per-read vector (4.2 MB)
+DUMP_CODES = 1 << 21  # float32 values of a sampled coverage or base vector (8.4 MB)
+DUMP_LIMIT = 64_000_000  # bytes of all files together
+
+
+def _sample(a, cap, seed):
+    """`a` when it has at most `cap` rows, else `cap` of its rows chosen with a fixed seed, in their order."""
+    if a.shape[0] <= cap:
+        return a
+    return a[np.sort(np.random.default_rng(seed).choice(a.shape[0], cap, replace=False))]
+
+
+def _overlap_arrays(prefix, ovl, seed):
+    """An overlap list (OVERLAP_DTYPE: lhs_id, lhs_begin, lhs_end, rhs_id, rhs_begin, rhs_end, score, strand)."""
+    cols = np.ascontiguousarray(ovl).view(np.uint32).reshape(-1, 8)
+    return {prefix + "_sample": _sample(cols, DUMP_ROWS, seed).astype(np.float64),
+            prefix + "_column_sums": cols.sum(axis=0, dtype=np.uint64).astype(np.float64)}
+
+
+def dump_outputs(path, out):
+    """Writes what the last timed step computed as path/<name>.npy.  Integers are exact in float64; the large arrays are
+    seeded samples (same sizes -> same positions), each beside a whole-array sum or count that any change moves:
+      overlaps_sample [rows, 8], overlaps_column_sums [8], overlap_offsets     the overlap pass's kept overlap lists
+      piles_sample (float32), piles_sum [1], pile_offsets                      its pile coverage words
+      pass2_overlaps_sample, pass2_overlaps_column_sums, pass2_contained       the second pass (--workload c5)
+      consensus_sample (float32 base codes), consensus_lengths,                the last polishing round's contigs
+      consensus_base_counts [contigs, 5] (codes 0..3, other), polished_ratio"""
+    arrays = {}
+    if "overlaps" in out:
+        (data, poff), (ovl, ooff) = out["piles"], out["overlaps"]
+        arrays.update(_overlap_arrays("overlaps", ovl, 1))
+        arrays["overlap_offsets"] = _sample(ooff, DUMP_VALUES, 2).astype(np.float64)
+        arrays["piles_sample"] = _sample(data, DUMP_CODES, 3).astype(np.float32)
+        arrays["piles_sum"] = np.array([data.sum(dtype=np.uint64)], dtype=np.float64)
+        arrays["pile_offsets"] = _sample(poff, DUMP_VALUES, 4).astype(np.float64)
+    if "pass2" in out:
+        arrays.update(_overlap_arrays("pass2_overlaps", out["pass2"]["overlaps"], 5))
+        arrays["pass2_contained"] = _sample(out["pass2"]["contained"], DUMP_VALUES, 6).astype(np.float32)
+    if "consensus" in out:
+        cons = [np.asarray(c, dtype=np.uint8) for c in out["consensus"]]
+        arrays["consensus_lengths"] = _sample(np.array([len(c) for c in cons], dtype=np.float64), DUMP_VALUES, 7)
+        arrays["consensus_base_counts"] = _sample(np.array([np.bincount(np.minimum(c, 4), minlength=5) for c in cons],
+                                                           dtype=np.float64).reshape(-1, 5), DUMP_VALUES // 5, 8)
+        arrays["consensus_sample"] = _sample(np.concatenate(cons) if cons else np.zeros(0, np.uint8), DUMP_CODES,
+                                             9).astype(np.float32)
+        arrays["polished_ratio"] = _sample(np.asarray(out["ratio"], dtype=np.float64), DUMP_VALUES, 10)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("[bench] --dump-outputs: %d arrays, %.1f MB in %s" % (len(arrays), total / 1e6, path), file=sys.stderr)
+
+
 def make_workload(args, device):
     """Seeded synthetic genome, reads and draft contigs of the workload, generated on the GPU (torch as the random /
     scatter engine), handed over as host arrays like any caller's data."""
@@ -228,10 +288,11 @@ def main():
     ap.add_argument("--polish-rounds", type=int, default=2)
     ap.add_argument("--cpu-sample-genome", type=int, default=None, help="genome of the CPU baseline's overlap sample "
                     "(default: 20 Mb on >= 96 cores, 8 Mb on >= 32, else 2 Mb)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--load-bases", type=int, default=150_000_000,
-                    help="bases of the gz FASTQ the input path (rvn_reads_load) is timed on, outside the timed region (0 = skip)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+                    help="--full: bases of the gz FASTQ the input path (rvn_reads_load) is timed on, outside the timed "
+                         "region (0 = skip)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel HIP events")
     ap.add_argument("--engine-option", action="append", default=[], metavar="NAME=VALUE",
                     help="rvn_engine_set_option before the run (tuning experiments; repeatable)")
     ap.add_argument("--targets-through-host", action="store_true", help="round r + 1's targets = an upload of the sequences "
@@ -241,7 +302,13 @@ def main():
                     "collective) instead of one genome sharded across the ranks")
     ap.add_argument("--sharded", action="store_true", help="run the sharded code path even at N = 1 (one rank owning "
                     "every read and hash class): measures what the partition / regroup steps cost before any link traffic")
+    ap.add_argument("--full", action="store_true", help="also measure per-kernel times and rooflines, the overlap pass "
+                    "through the host boundary, the input path and the CPU baseline (off: only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64, seeded samples of the large arrays, under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     args.errors = (0.04, 0.03, 0.03)
     if args.workload == "c4":
         args.genome = args.genome or 100_000_000
@@ -306,8 +373,9 @@ def main():
         preads.attach_quality((np.full(int(qoff[-1]), 33 + 10, dtype=np.uint8), qoff), block_shift=6)
     eng.set_timing(False)  # no per-stage host syncs inside the timed region
     peng.set_timing(False)
-    eng.set_kernel_timing(not args.no_kernel_timing)
-    peng.set_kernel_timing(not args.no_kernel_timing)
+    kernel_timing = args.full and not args.no_kernel_timing
+    eng.set_kernel_timing(kernel_timing)
+    peng.set_kernel_timing(kernel_timing)
 
     comm = None
     if sharded_mode:
@@ -318,15 +386,28 @@ def main():
     if sharded_mode:  # this rank's reads, resident for every step like `reads` of the single-GPU pass
         b = sharded.partition_reads(rs.lengths, world)
         own_reads = eng.upload(sharded.slice_reads(rs, int(b[rank]), int(b[rank + 1])))
-    legs = {"overlap_s": 0.0, "polish_s": 0.0, "overlap_steps": [], "polish_steps": [], "poa_ms": 0.0, "poa_rounds": 0}
+    legs = {"overlap_s": 0.0, "polish_s": 0.0, "overlap_steps": [], "polish_steps": [], "poa_ms": 0.0, "poa_rounds": 0,
+            "paused_s": 0.0}
     last = {}
+    outputs = {}  # --dump-outputs: what the last timed step computed
 
-    def step(timed):
+    def fetch_pass(p):
+        """The piles and overlap lists a caller of the pass receives; returns the seconds the fetch took (the step's time
+        leaves them out: the timed path keeps its results in HBM)."""
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        outputs["piles"], outputs["overlaps"] = p.piles(), p.overlaps()
+        return time.perf_counter() - t
+
+    def step(timed, keep=False):
         t_a = time.perf_counter()
+        paused = 0.0
         if sharded_mode:
             res = sharded.find_overlaps_and_create_piles_sharded_dev(eng, rs, comm, dev, freq=args.freq, kmax=args.kmax,
                                                                      own=own_reads, laps=shard_laps if timed else None,
                                                                      fetch=False)  # results stay in HBM, as in the 1-GPU leg
+            if keep:
+                paused = fetch_pass(res["pass1"])
             res["pass1"].close()
             last["overlap"] = {k: res[k] for k in ("lo", "hi", "occurrence", "stats")}
         else:
@@ -363,7 +444,11 @@ def main():
                     st5["second_pass_s"] += t_s4 - t_s3
                     last["c5"] = {"pass1_overlaps": int(ovl.shape[0]), "kept_by_identity": int(kept.shape[0]),
                                   "invalid_or_contained": float(inv2.mean()), "pass2_overlaps": int(res2["overlaps"].shape[0])}
+                if keep:
+                    outputs["pass2"] = res2
                 del res2, ovl, kept, upd
+            if keep:
+                paused = fetch_pass(p)
             p.close()
             if os.environ.get("RVN_DEBUG_PASS1"):
                 print("[bench] pass1 call %.1f ms, close %.1f ms" % ((t_x - t_a) * 1e3, (time.perf_counter() - t_x) * 1e3),
@@ -395,12 +480,15 @@ def main():
                 legs["poa_ms"] += float(st["poa_ms"])
                 legs["poa_rounds"] += 1
             last["ratio"] = float(np.mean(ratio)) if len(ratio) else 0.0
+            if keep:
+                outputs["consensus"], outputs["ratio"] = cur, ratio
         t_c = time.perf_counter()
         if timed:
-            legs["overlap_s"] += t_b - t_a
+            legs["overlap_s"] += t_b - t_a - paused
             legs["polish_s"] += t_c - t_b
-            legs["overlap_steps"].append(round(t_b - t_a, 4))
+            legs["overlap_steps"].append(round(t_b - t_a - paused, 4))
             legs["polish_steps"].append(round(t_c - t_b, 4))
+            legs["paused_s"] += paused
             last["n_windows"] = n_windows
 
     for _ in range(args.warmup):
@@ -410,10 +498,10 @@ def main():
         peng.reset_stats()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for i in range(args.steps):
+        step(True, keep=args.dump_outputs is not None and i == args.steps - 1)
     barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - legs["paused_s"]
 
     units = float(rs.total_bases) if (world == 1 or not sharded_mode) else float(rs.total_bases) / world
     dt, total_bases = rdist.aggregate(dt, units, dist, device="cuda")
@@ -422,19 +510,22 @@ def main():
 
     counters_raw = eng.counters()
     kms = {}
-    if not args.no_kernel_timing:
+    if kernel_timing:
         kms = dict(eng.kernel_ms())
         if peng is not eng:
             for k2, v in peng.kernel_ms().items():
                 a = kms.get(k2, (0.0, 0))
                 kms[k2] = (a[0] + v[0], a[1] + v[1])
     poa_cells = peng.poa_cells()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    outputs.clear()
 
     # through-the-boundary time of the overlap pass, once, outside the timed region: what a caller that hands over host
     # buffers and wants host vectors back pays (upload + pass + fetch of piles and overlap lists); the polishing rounds
     # above already include their uploads (draft contigs) and fetches (consensus)
     boundary = None
-    if rank == 0 and not sharded_mode:
+    if args.full and rank == 0 and not sharded_mode:
         torch.cuda.synchronize()
         tb0 = time.perf_counter()
         r2 = eng.upload(rs)
@@ -465,7 +556,7 @@ def main():
     # bounded so that the default run stays within minutes: once as blocked gzip (bgzip's multi-member form: the pool
     # inflates members in parallel) and once as ONE gzip member (one deflate stream = one thread, front to back)
     load_stats = None
-    if rank == 0 and not sharded_mode and args.load_bases > 0:
+    if args.full and rank == 0 and not sharded_mode and args.load_bases > 0:
         import gzip
         import tempfile
         from raven_amd import seqio as _seqio
@@ -689,7 +780,7 @@ def main():
             "counters_per_step": counters,
             "last_polish_round": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in last.get("polish", {}).items()},
             "roofline": roofline,
-            "roofline_traffic_source": traffic_provenance(),
+            "roofline_traffic_source": traffic_provenance() if kms else None,
             "roofline_hbm": roofline_hbm,
             "roofline_hbm_kernels": roofline_hbm_all,
             "roofline_poa": roofline_poa if roofline is not roofline_poa else None,
@@ -702,7 +793,7 @@ def main():
         }
         if sharded_mode:
             out["rank0"] = last.get("overlap")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, os.cpu_count() or 1)
         print(json.dumps(out), flush=True)
     if dist is not None:

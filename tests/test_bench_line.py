@@ -1,4 +1,4 @@
-"""The bench contract on the committed line (profiles/r06_bench_c4.json = `python bench.py` on one MI355X): the keys the
+"""The bench contract on the committed line (profiles/r06_bench_c4.json = `python bench.py --full` on one MI355X): the keys the
 driver reads, the two objects the measurement rules ask for (`roofline`, `cpu_baseline`) and their internal arithmetic.
 No GPU needed: this reads the committed evidence; `bench.py --help` shows the flags of the contract exist."""
 import json
@@ -46,5 +46,5 @@ def test_bench_flags_of_the_contract_exist():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=300)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--full", "--dump-outputs"):
         assert flag in out.stdout, flag

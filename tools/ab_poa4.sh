@@ -9,7 +9,7 @@ for l in sys.stdin:
 done
 done
 for lib in lib_b lib_a; do
-  RVN_LIB_PATH=$PWD/raven_amd/$lib/libraven_hip_test.so timeout 600 python bench.py --workload c4 --steps 2 --warmup 2 --no-cpu-baseline --load-bases 0 2>/dev/null | python -c "
+  RVN_LIB_PATH=$PWD/raven_amd/$lib/libraven_hip_test.so timeout 600 python bench.py --full --workload c4 --steps 2 --warmup 2 --no-cpu-baseline --load-bases 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); k = d['kernels']
 print('$lib', 'ms/step', d['ms_per_step'], 'poa_ms', d['last_polish_round']['poa_ms'], 'poa_rows avg', k['poa_rows']['avg_launch_ms'], 'banded', k.get('poa_banded',{}).get('ms_per_step'), 'to64', d['last_polish_round']['poa_windows_to_64_columns'])"

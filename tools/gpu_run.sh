@@ -47,7 +47,7 @@ for l in sys.stdin:
        env $envs timeout 900 python bench.py --workload $name --steps ${STEPS:-2} --warmup ${WARMUP:-2} --no-cpu-baseline --load-bases 0 $BENCH_ARGS > $f 2> ${f%.json}.err; summ $f;;
     bench-full) f=gpurun_out/${TAG}_bench_${arg}.json   # the line the driver takes (default steps; CPU baseline at c4)
        extra="--no-cpu-baseline"; [ "$arg" = "c4" ] && extra=""
-       timeout 1500 python bench.py --workload $arg $extra > $f 2> ${f%.json}.err; summ $f;;
+       timeout 1500 python bench.py --full --workload $arg $extra > $f 2> ${f%.json}.err; summ $f;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3;;
     parity) n=${arg%%/*}; shape=ont; [ "$arg" != "$n" ] && shape=${arg#*/}   # parity:20000 or parity:20000/qual
        f=gpurun_out/${TAG}_poa_parity_${shape}_$n.json
@@ -65,7 +65,7 @@ print('pass', {k: v for k, v in d['overlap_pass_at_n_ranks'].items() if k != 'st
 for r in d['polishing_rounds_at_n_ranks']: print(r)" || tail -5 ${f%.json}.err;;
     profile) bash tools/profile_round.sh $arg
        # (a bench-full step later in the same call reads the traffic file from profiles/: without this its line says stale)
-       for f in pmc_traffic.json pmc_calibration.json kernel_stats.csv bench_under_rocprof.json; do [ -f gpurun_out/${arg}_$f ] && cp gpurun_out/${arg}_$f profiles/; done;;
+       for f in pmc_traffic.json pmc_calibration.json kernel_stats.csv bench_under_rocprof.json; do [ -f profile_out/${arg}_$f ] && cp profile_out/${arg}_$f profiles/; done;;
     sqpoa) bash tools/prof_poa.sh $arg;;
     mempoa) bash tools/prof_poa_mem.sh $arg;;
     tracenw) bash tools/trace_nw.sh $arg;;

@@ -26,7 +26,7 @@ for w in c2 c4; do
     for mode in 1 0 2; do
       [ $w = c4 ] && [ $rep = 2 ] && continue
       f=gpurun_out/${TAG}_walk_${w}_mode${mode}_${rep}.json
-      timeout 600 python bench.py --workload $w --steps 2 --warmup 2 --no-cpu-baseline --load-bases 0 --engine-option nw_group_walk=$mode > $f 2> ${f%.json}.err
+      timeout 600 python bench.py --full --workload $w --steps 2 --warmup 2 --no-cpu-baseline --load-bases 0 --engine-option nw_group_walk=$mode > $f 2> ${f%.json}.err
       line $f
     done
   done
