@@ -251,7 +251,8 @@ typedef struct rvn_polish_stats {
   uint64_t n_overlaps, n_reads_used, n_layers, n_windows, n_polished_windows, n_failed_windows;
   double poa_ms;                    /* device time of the window-consensus batch */
   double map_ms, host_ms, total_ms; /* wall: index + map + best overlap | host planning (jobs, window tables) | whole call */
-  uint64_t n_dropped_layers;        /* reads left out because their alignment is beyond the path kernel (band > ~32 000) */
+  uint64_t n_dropped_layers;        /* reads left out because their alignment is beyond the path stage (band > 262 144 rows, or
+                                       its stored band alone above the stage's HBM budget, engine option nw_budget_mb) */
   double align_ms;                  /* device time of the alignment-path stage (banded NW forward + traceback) */
   uint64_t n_aligned, n_align_retries; /* read-to-target alignments done | attempts repeated with a doubled band */
   uint64_t align_band_cells;        /* DP cells inside the computed bands (all attempts) */
@@ -443,6 +444,9 @@ int rvn_overlap_update_and_type(rvn_overlap* overlaps, uint64_t n, const uint32_
  *   nw_group_walk      alignment-path stage: which walk a launch takes — 1 a lane per alignment, 2 a group of sixteen lanes per
  *                      alignment, 3 a lane per alignment with half-size strips, otherwise (default) the group for launches of at
  *                      most 8 192 alignments and the half-size strips beyond 65 536; same records either way
+ *   nw_stripe_lanes    alignment-path stage: the widest ring of one sweep, in lanes (1 .. 64; default 64, a whole wave).  A band
+ *                      wider than that ring is swept in stripes of that many lanes (at most 8 rings: 262 144 rows by default);
+ *                      smaller values force striping on small inputs; same records either way
  *   index_direct_min_keys  index: distinct values from which all 4^k possible values are addressed directly (an 8-GB table at
  *                      k = 15, one cache line per probe; default 8 388 608; 1 = every index with k <= 15); same matches either way
  *   poa_rows_min_windows  window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (default 8 192;

@@ -37,6 +37,12 @@ int rvn_test_low_complexity(const uint8_t* codes, uint32_t k);
  * Bits 8-15 of rc: 0 = the walk of one lane per alignment (whole strips), 1 = the same with strips of sixteen kept columns (what
  * the kernel runs where the strips live in LDS); 4 / 16 / 64 = the group walk with that many lanes per alignment
  * (nwtrace.h: NwGroupWalk, its phases stepped lane by lane) — band then has a fourth entry, the batches the walk took.
+ * Bits 16-23 of rc: 0 = one ring, else the striped sweep with stripes of that many lanes (1 .. 64; R = force_r, 0 = 1)
+ * whatever the band — band then has five entries {k, lanes one ring would need, R, batches of a group walk, stripes};
+ * a band wider than 8 such rings is refused (-3).  Bit 24 of rc: the production stage on the GPU instead (nwpath.hip
+ * nw_breakpoints as a polishing round runs it, in an engine of its own on device 0; bits 16-23 = engine option
+ * nw_stripe_lanes, 0 = default; k / force_r / bits 8-15 unused): band then has five entries {k, stripe lanes (0: one
+ * ring), R, stripes, microseconds of the stage} of the job's final plan; -3 if the stage did not align it.
  * Returns 0, 1 if the walk did not end at cost 0, < 0 on invalid arguments. */
 int rvn_test_nw_breakpoints(const uint64_t* t_words, uint32_t t_len, const uint64_t* r_words, uint32_t r_len,
                             uint32_t t_begin, uint32_t n, uint32_t q_begin, uint32_t m, int rc, uint32_t w, uint32_t k,

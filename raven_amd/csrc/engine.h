@@ -108,6 +108,8 @@ struct EngineOptions {
   long long nw_group_walk = 0;       // alignment-path stage: 1 = every walk one lane per alignment, 2 = every walk a group of lanes per
                                      // alignment (nwtrace.h), 3 = one lane per alignment with strips of sixteen kept columns, otherwise
                                      // by the number of alignments in the launch.  Same records either way
+  long long nw_stripe_lanes = 0;     // alignment-path stage: lanes of the widest ring of one sweep (1 .. 64, default 64 = a wave); a band
+                                     // wider than that is swept in stripes of that many super-blocks (nwpath.h).  Same records either way
   long long index_direct_min_keys = 0;  // index: distinct values from which every possible value is addressed directly (index.hip; default 8 M,
                                      // 1 = every index with 2k <= 30 bits — the tests of that path on small inputs).  Same matches either way
   long long poa_rows_min_windows = -1;  // window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (poa4.hip);
@@ -314,7 +316,7 @@ void poa_banded_emulate(const u8* h_codes, const u8* h_quals, const u64* h_layer
 
 struct PolishStats {
   u64 n_overlaps = 0, n_reads_used = 0, n_layers = 0, n_windows = 0, n_polished_windows = 0, n_failed_windows = 0;
-  u64 n_dropped_layers = 0;  // reads whose alignment is beyond the path kernel (band threshold > ~32 000): not used
+  u64 n_dropped_layers = 0;  // reads whose alignment is beyond the path stage (band > 262 144 rows, or above the HBM budget): not used
   double poa_ms = 0;                            // device time of the POA batch
   double map_ms = 0, host_ms = 0, total_ms = 0;  // wall: index + map | host planning (jobs, window tables) | all
   double align_ms = 0;                           // device time of the alignment-path stage (forward + traceback)
@@ -329,8 +331,9 @@ struct NwStats {
   u64 band_cells = 0, sum_distance = 0, store_bytes = 0;
   double ms = 0;
 };
+// distances (optional): per job the exact distance, ~0 for a job that was not aligned
 void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& R, std::vector<NwJob>& jobs, u32 w, NwWindowRec* d_recs,
-                    u64 n_recs, NwStats& st);
+                    u64 n_recs, NwStats& st, std::vector<u32>* distances = nullptr);
 // the same code stepped on the CPU (64 emulated lanes): test hook, see rvn_test_nw_breakpoints
 int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r_len, u32 t_begin, u32 n, u32 q_begin, u32 m,
                         int rc, u32 w, u32 k, int force_R, NwWindowRec* recs, u32* distance, u32* band);

@@ -313,13 +313,14 @@ void stop() {
 }  // namespace devpool
 
 const char* engine_option_names() {
-  return "nw_budget_mb, nw_group_walk, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
+  return "nw_budget_mb, nw_group_walk, nw_stripe_lanes, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
          "no_arena, release_always, polish_join, polish_sketch_cache_mb";
 }
 long long* engine_option(EngineOptions& o, const char* name) {
   const std::string n(name ? name : "");
   if (n == "nw_budget_mb") return &o.nw_budget_mb;
   if (n == "nw_group_walk") return &o.nw_group_walk;
+  if (n == "nw_stripe_lanes") return &o.nw_stripe_lanes;
   if (n == "index_direct_min_keys") return &o.index_direct_min_keys;
   if (n == "poa_rows_min_windows") return &o.poa_rows_min_windows;
   if (n == "io_threads") return &o.io_threads;
@@ -2303,12 +2304,69 @@ int rvn_test_freelist(uint64_t size, uint64_t grain, const int64_t* ops, uint32_
   return RVN_OK;
 }
 
+// Bit 24 of rc: the PRODUCTION stage on the device (nw_breakpoints, as a polishing round runs it: planning, variants,
+// stripes, retries, walks) on this one job, in an engine of its own (device 0); bits 16-23 = nw_stripe_lanes (0: default),
+// k and force_r unused.  band[5] = {k, stripe lanes (0: one ring), R, stripes, microseconds of the stage}; -3: not aligned.
+static int nw_breakpoints_device(const uint64_t* t_words, uint32_t t_len, const uint64_t* r_words, uint32_t r_len,
+                                 uint32_t t_begin, uint32_t n, uint32_t q_begin, uint32_t m, int rc, uint32_t w, uint32_t,
+                                 int, uint32_t* recs, uint32_t* distance, uint32_t* band) {
+  rvn_engine* h = nullptr;
+  int r = rvn_engine_create(&h, 15, 5, 500, 4, 100, 10000, 0);
+  if (r != RVN_OK) return r;
+  rvn_reads *T = nullptr, *Rd = nullptr;
+  const u64 tw = (static_cast<u64>(t_len) + 31) / 32, rw = (static_cast<u64>(r_len) + 31) / 32;
+  const u64 toff[2] = {0, tw}, roff[2] = {0, rw};
+  const u32 tid = 0;
+  r = rvn_reads_upload(h, t_words, tw, toff, &t_len, &tid, 1, &T);
+  if (r == RVN_OK) r = rvn_reads_upload(h, r_words, rw, roff, &r_len, &tid, 1, &Rd);
+  if (r == RVN_OK) {
+    const u32 lanes = static_cast<u32>(rc >> 16) & 0xFFu;
+    if (lanes) h->e.opt.nw_stripe_lanes = lanes;
+    r = guarded(&h->e, [&]() -> int {
+      std::vector<NwJob> jobs(1);
+      NwJob& J = jobs[0];
+      J = NwJob{};
+      J.t_word = 0;
+      J.r_word = 0;
+      J.t_begin = t_begin;
+      J.n = n;
+      J.q_begin = q_begin;
+      J.m = m;
+      J.r_len = r_len;
+      J.rc = rc & 1;
+      J.n_windows = (t_begin + n - 1) / w - t_begin / w + 1;
+      J.bp_off = 0;
+      DevBuf d_recs;
+      NwWindowRec* dr = d_recs.get<NwWindowRec>(J.n_windows + 1);
+      NwStats st;
+      std::vector<u32> dist;
+      nw_breakpoints(h->e, T->r, Rd->r, jobs, w, dr, J.n_windows, st, &dist);
+      RVN_HIP(hipMemcpy(recs, dr, static_cast<size_t>(J.n_windows) * sizeof(NwWindowRec), hipMemcpyDeviceToHost));
+      *distance = dist[0];
+      if (band) {
+        band[0] = jobs[0].k;
+        band[1] = jobs[0].S;
+        band[2] = jobs[0].R;
+        band[3] = static_cast<u32>(nw_geo_job(jobs[0]).n_stripes);
+        band[4] = static_cast<u32>(st.ms * 1000.0);
+      }
+      return dist[0] == ~0u ? -3 : RVN_OK;
+    });
+  }
+  if (Rd) rvn_reads_destroy(Rd);
+  if (T) rvn_reads_destroy(T);
+  rvn_engine_destroy(h);
+  return r;
+}
+
 int rvn_test_nw_breakpoints(const uint64_t* t_words, uint32_t t_len, const uint64_t* r_words, uint32_t r_len,
                             uint32_t t_begin, uint32_t n, uint32_t q_begin, uint32_t m, int rc, uint32_t w, uint32_t k,
                             int force_r, uint32_t* recs, uint32_t* distance, uint32_t* band) {
   if (!t_words || !r_words || !recs || !distance || w == 0) return RVN_EINVAL;
   if (static_cast<u64>(t_begin) + n > t_len || static_cast<u64>(q_begin) + m > r_len) return RVN_EINVAL;
   static_assert(sizeof(NwWindowRec) == 32, "record layout");
+  if ((rc >> 24) & 1) return nw_breakpoints_device(t_words, t_len, r_words, r_len, t_begin, n, q_begin, m, rc, w, k, force_r,
+                                                   recs, distance, band);
   return nw_breakpoints_host(t_words, t_len, r_words, r_len, t_begin, n, q_begin, m, rc, w, k, force_r,
                              reinterpret_cast<NwWindowRec*>(recs), distance, band);
 }

@@ -52,7 +52,7 @@ struct NwJob {
   u32 G;           // lanes per alignment of the sweep kernel (ring of L <= G lanes)
   u32 read, target;  // indices in their sets
   u32 n_windows;     // windows touched by the target span
-  u32 pad_;
+  u32 S;             // 0: one ring holds the band; else super-blocks (= ring lanes) per stripe of a striped sweep (NwGeo)
 };
 static_assert(sizeof(NwJob) == 96, "NwJob layout");
 
@@ -103,10 +103,47 @@ struct NwGeo {
   __host__ __device__ int jfed(int s) const {  // last column at which the super-block above is still inside the band
     return s > 0 ? 64 * s * R + lo : 0;
   }
+  // Striped sweep (S > 0): a band wider than one wave's ring is cut into stripes of S consecutive super-blocks (rows
+  // 64 R S st ..); stripe st is swept by a ring of L = S lanes, each holding ONE super-block from its entry to its
+  // retirement, over the steps those super-blocks live.  Myers' recurrence flows down and to the right only: the one input
+  // from outside the stripe is its top boundary — the horizontal delta out of the last block of stripe st - 1 at every
+  // column (that stripe's hs stream) — plus, where the stripe's first super-block enters the band, the score at the bottom
+  // of the one above (one word behind the stripe's hs region).  Every stripe stores gps hs groups and qps checkpoints,
+  // from its own first step on (the stripes' step ranges overlap: step t of super-block s is column t - s, as unstriped).
+  // s0 .. s1: the super-blocks of the stripe a sweep works on (unstriped: all of them).
+  int S, n_stripes, gps, qps;
+  int s0, s1;
+  __host__ __device__ int st_t0(int st) const {  // first step of stripe st's loop (1 mod 32): its first entry, rounded down
+    const int sa = st * S;
+    return ((ja(sa) + sa - 1) & ~31) + 1;
+  }
+  __host__ __device__ u64 stripe_hs_words() const { return static_cast<u64>(gps) * static_cast<u64>(L) * R + 1; }
+  __host__ __device__ u64 stripe_ck_entries() const { return static_cast<u64>(qps) * static_cast<u64>(L) * R; }
+  // word of (super-block s, block r of it, hs group gi) / entry of (s, r, checkpoint q) in the job's region
+  __host__ __device__ u64 hs_at(int s, int r, int gi) const {
+    const u64 lane = static_cast<u64>(s % L) * R + static_cast<u64>(r);
+    if (S == 0) return static_cast<u64>(gi) * static_cast<u64>(L) * R + lane;
+    const int st = s / S;
+    int x = gi - ((st_t0(st) - 1) >> 4);
+    x = x < 0 ? 0 : (x >= gps ? gps - 1 : x);  // (reads only: never outside the stripe's region)
+    return static_cast<u64>(st) * stripe_hs_words() + static_cast<u64>(x) * static_cast<u64>(L) * R + lane;
+  }
+  __host__ __device__ u64 ck_at(int s, int r, int q) const {
+    const u64 lane = static_cast<u64>(s % L) * R + static_cast<u64>(r);
+    if (S == 0) return static_cast<u64>(q) * static_cast<u64>(L) * R + lane;
+    const int st = s / S;
+    int x = q - ((st_t0(st) - 1) >> 5);
+    x = x < 0 ? 0 : (x >= qps ? qps - 1 : x);
+    return static_cast<u64>(st) * stripe_ck_entries() + static_cast<u64>(x) * static_cast<u64>(L) * R + lane;
+  }
+  // the score handed from stripe st to stripe st + 1 (see above)
+  __host__ __device__ u64 hand_at(int st) const { return static_cast<u64>(st) * stripe_hs_words() + stripe_hs_words() - 1; }
   __host__ __device__ u64 hs_words() const {
+    if (S) return static_cast<u64>(n_stripes) * stripe_hs_words();
     return static_cast<u64>((n_steps + kNwHsSteps - 1) / kNwHsSteps) * static_cast<u64>(L) * static_cast<u64>(R);
   }
   __host__ __device__ u64 ck_entries() const {
+    if (S) return static_cast<u64>(n_stripes) * stripe_ck_entries();
     return static_cast<u64>(n_steps / kNwCkSteps) * static_cast<u64>(L) * static_cast<u64>(R);
   }
 };
@@ -121,8 +158,27 @@ __host__ __device__ inline NwGeo nw_geo(u32 n, u32 m, u32 k, u32 R) {
   g.nb = static_cast<int>((static_cast<u64>(n) + 63) >> 6);
   g.n_super = (g.nb + g.R - 1) / g.R;
   g.n_steps = g.m + g.n_super;
+  g.S = 0;
+  g.n_stripes = 1;
+  g.gps = g.qps = 0;
+  g.s0 = 0;
+  g.s1 = g.n_super;
   return g;
 }
+// the same band swept in stripes of S super-blocks (S lanes per stripe's ring); ring_lanes = what one ring would need
+__host__ __device__ inline NwGeo nw_geo_striped(u32 n, u32 m, u32 k, u32 R, u32 S) {
+  NwGeo g = nw_geo(n, m, k, R);
+  if (S == 0) return g;
+  g.S = static_cast<int>(S);
+  g.L = g.S;
+  g.n_stripes = (g.n_super + g.S - 1) / g.S;
+  // steps of a stripe's loop: at most 64 R S + lo + hi + S - 1 from its first entry to its last retirement, + 31 before
+  // (rounded down to a checkpoint) and + 15 behind (whole hs groups); two groups of reserve
+  g.gps = (64 * g.R * g.S + g.lo + g.hi + g.S + 46) / kNwHsSteps + 2;
+  g.qps = g.gps / 2 + 1;
+  return g;
+}
+__host__ __device__ inline NwGeo nw_geo_job(const NwJob& J) { return nw_geo_striped(J.n, J.m, J.k, J.R, J.S); }
 
 struct NwPm {
   u64 pv, mv;

@@ -8,6 +8,9 @@
 //                           first.  Block state in registers, match masks in LDS; per step one ds_bpermute, one LDS
 //                           read, the Myers update.  Leaves the exact distance (if <= k), the hs stream and the
 //                           checkpoints.
+//   nw_sweep_kernel<8, 64, true>   one stripe of the alignments whose band is wider than one wave's ring (nwpath.h, NwGeo:
+//                           the band in horizontal stripes of super-blocks, successive launches, the top input of a stripe
+//                           from the hs stream of the one above).
 //   nw_trace_kernel         the backward walk (nwtrace.h), one lane per alignment, strip of <= 33 columns in LDS.
 //
 // Host side: threshold k from the running error-rate estimate of the engine (first call: a generous default), the
@@ -47,6 +50,12 @@ constexpr u32 kSideSweepMaxWaves = 2048;    // a sweep launch of at most this ma
 constexpr u32 kLevels = 8;
 const u32 kRs[kLevels] = {1, 1, 1, 1, 1, 2, 4, 8};
 const u32 kGs[kLevels] = {4, 8, 16, 32, 64, 64, 64, 64};
+// A band no variant's ring holds is swept in stripes (nwpath.h, NwGeo): R = 8, stripes of nw_stripe_lanes super-blocks
+// (default 64, a whole wave), a band of at most kNwMaxStripes such rings (262 144 rows with whole waves, 8 x the widest
+// ring).  Striped jobs are a class of their own, above the variants.
+constexpr u32 kNwMaxStripes = 8;
+constexpr u32 kStriped = kLevels;
+constexpr u32 kClasses = kLevels + 1;
 
 template <int G>
 __device__ __forceinline__ u32 group_max(u32 v) {
@@ -63,12 +72,16 @@ constexpr int sweep_waves_per_simd() {
   return R == 1 ? 8 : (R == 2 ? 6 : (R == 4 ? 4 : 2));
 }
 
-template <int R, int G>
+// STRIPED: stripe `stripe` of every (striped) job of the launch — one super-block per lane, the stripe's steps only, the
+// top input from the stripe above (NwTopIn); the last stripe of a job leaves its result
+template <int R, int G, bool STRIPED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sweep_waves_per_simd<R>())))
 void nw_sweep_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx, u32 n_idx,
                      const u64* __restrict__ t_words, const u64* __restrict__ r_words, u32* __restrict__ hs,
-                     NwPm* __restrict__ ck, u32* __restrict__ result, u32* __restrict__ status, u32* __restrict__ next) {
+                     NwPm* __restrict__ ck, u32* __restrict__ result, u32* __restrict__ status, u32* __restrict__ next,
+                     int stripe) {
   constexpr int NG = 64 / G;
+  static_assert(!STRIPED || G == 64, "a stripe's loop range is per job: one job per wave");
   __shared__ u64 s_peq[4][R * 4 * 64];
   const int lane = lane_id();
   const int group = lane / G, lig = lane % G, gbase = group * G;
@@ -82,21 +95,46 @@ void nw_sweep_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx
     if (q0 >= n_idx) break;
     const u32 q = q0 + static_cast<u32>(group);
     const bool has = q < n_idx;
-    NwSweepLane<R, 64> ln;
+    NwSweepLane<R, 64, STRIPED> ln;
     u32 ji = 0, k = 0;
     int L = 0, n_steps = 0;
     u32* hs_j = hs;
     NwPm* ck_j = ck;
+    // striped: first step of the loop, the stripe's stores (groups g0 .., checkpoints q0 ..), the top input, the step at
+    // which the score the next stripe enters with is taken, whether this is the job's last stripe
+    int t0 = 1, g0 = 0, qc0 = 0, gps = 0, qps = 0, t_hand = kNwNever, sc_in = 0, sc_hand = 0, lig_hand = -1;
+    bool is_top = false, last = true;
+    NwTopIn top;
     if (has) {
       ji = idx[q];
       const NwJob J = jobs[ji];
-      const NwGeo geo = nw_geo(J.n, J.m, J.k, R);
+      NwGeo geo = STRIPED ? nw_geo_job(J) : nw_geo(J.n, J.m, J.k, R);
+      n_steps = geo.n_steps;
+      if (STRIPED) {
+        geo.s0 = stripe * geo.S;
+        geo.s1 = geo.s0 + geo.S < geo.n_super ? geo.s0 + geo.S : geo.n_super;
+        t0 = geo.st_t0(stripe);
+        g0 = (t0 - 1) >> 4;
+        qc0 = (t0 - 1) >> 5;
+        gps = geo.gps;
+        qps = geo.qps;
+        n_steps = geo.je(geo.s1 - 1) + geo.s1;  // the retirement of its last super-block
+        last = geo.s1 == geo.n_super;
+        if (!last && geo.ja(geo.s1) > 1) {
+          t_hand = geo.ja(geo.s1) + geo.s1;
+          lig_hand = geo.s1 - 1 - geo.s0;
+        }
+        is_top = lig == 0 && stripe > 0;
+        if (is_top) {
+          top.init(hs + J.hs, geo, t0);
+          sc_in = static_cast<int>(hs[J.hs + geo.hand_at(stripe - 1)]);
+        }
+      }
       ln.init(J, t_words, r_words, geo, lig, peq, lane);
       L = geo.L;
-      n_steps = geo.n_steps;
       k = J.k;
-      hs_j = hs + J.hs;
-      ck_j = ck + J.ckpt;
+      hs_j = hs + J.hs + (STRIPED ? static_cast<u64>(stripe) * geo.stripe_hs_words() : 0ULL);
+      ck_j = ck + J.ckpt + (STRIPED ? static_cast<u64>(stripe) * geo.stripe_ck_entries() : 0ULL);
     } else {
       ln.init_idle(peq, lane);
     }
@@ -109,35 +147,46 @@ void nw_sweep_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx
     n_steps_w = __builtin_amdgcn_readfirstlane((n_steps_w + 15) & ~15);
     const int prev = lig == 0 ? gbase + (L > 0 ? L - 1 : 0) : lane - 1;
     const bool st_ok = has && lig < L;
-    const int n_g = (n_steps + kNwHsSteps - 1) / kNwHsSteps, n_q = n_steps / kNwCkSteps;
+    int n_g = (n_steps + kNwHsSteps - 1) / kNwHsSteps, n_q = n_steps / kNwCkSteps;
+    if (STRIPED) {  // (the stripe's region: gps groups from g0, qps checkpoints from qc0)
+      n_g = g0 + gps;
+      n_q = qc0 + qps;
+    }
     const u64 row = static_cast<u64>(L) * R;
-    for (int t = 1; t <= n_steps_w; ++t) {
-      const int x = __shfl(ln.xf, prev, 64);
+    for (int t = t0; t <= n_steps_w; ++t) {
+      int x = __shfl(ln.xf, prev, 64);
+      if (STRIPED) {
+        if (is_top) x = top.x(t);
+        if (t == t_hand) sc_hand = ln.sc;  // (after step t - 1: what the ring's next lane would read at t)
+      }
       if (__ballot(ln.has_event(t)) != 0) {
-        const int sp = __shfl(ln.sc, prev, 64);
+        int sp = __shfl(ln.sc, prev, 64);
+        if (STRIPED && is_top) sp = sc_in;
         if (ln.has_event(t)) ln.event(t, x, sp);
       }
       ln.step(t, x);
       if ((t & 15) == 0) {
         const int gi = (t >> 4) - 1;
         if (st_ok && gi < n_g) {
-          u32* p = hs_j + static_cast<u64>(gi) * row + static_cast<u64>(lig) * R;
+          u32* p = hs_j + static_cast<u64>(gi - g0) * row + static_cast<u64>(lig) * R;
 #pragma unroll
           for (int r = 0; r < R; ++r) p[r] = ln.acc[r];
         }
         if ((t & 31) == 0) {
           const int qi = (t >> 5) - 1;
           if (st_ok && qi < n_q) {
-            NwPm* p = ck_j + static_cast<u64>(qi) * row + static_cast<u64>(lig) * R;
+            NwPm* p = ck_j + static_cast<u64>(qi - qc0) * row + static_cast<u64>(lig) * R;
 #pragma unroll
             for (int r = 0; r < R; ++r) p[r] = NwPm{ln.Pv[r], ln.Mv[r]};
           }
         }
         ln.next_group(t);
+        if (STRIPED && is_top) top.next_group(t);
       }
     }
+    if (STRIPED && has && lig == lig_hand) hs_j[row * static_cast<u64>(gps)] = static_cast<u32>(sc_hand);  // (NwGeo::hand_at)
     const u32 res1 = group_max<G>(ln.result);  // exactly one lane of the group holds D(n, m) + 1
-    if (has && lig == 0) {
+    if (has && lig == 0 && last) {
       const u32 res = res1 - 1u;
       result[ji] = res;
       status[ji] = (res1 != 0 && res <= k) ? 0u : 2u;  // 2: beyond the threshold, the host repeats the job with 2k
@@ -166,7 +215,7 @@ __global__ __launch_bounds__(64) void nw_trace_kernel(const NwJob* __restrict__ 
   const u32 ji = idx[q];
   if (status[ji] != 0) return;
   const NwJob J = jobs[ji];
-  const NwGeo geo = nw_geo(J.n, J.m, J.k, J.R);
+  const NwGeo geo = nw_geo_job(J);
   u64* g_pv = scratch + static_cast<u64>(blockIdx.x) * (2 * kNwStripCols * 64);
   const NwStripMem<64> mem{STRIP_LDS ? s_pv : g_pv, STRIP_LDS ? s_mv : g_pv + kNwStripCols * 64, static_cast<int>(threadIdx.x)};
   status[ji] = static_cast<u32>(nw_trace_job<64, SC>(J, geo, t_words, r_words, hs + J.hs, ck + J.ckpt, mem, result[ji], w, recs));
@@ -191,7 +240,7 @@ __global__ __launch_bounds__(64) void nw_trace_group_kernel(const NwJob* __restr
   const u32 ji = idx[q];
   if (status[ji] != 0) return;
   const NwJob J = jobs[ji];
-  const NwGeo geo = nw_geo(J.n, J.m, J.k, J.R);
+  const NwGeo geo = nw_geo_job(J);
   NwGroupWalk<64, GL> G;
   G.init(J, t_words, r_words, NwStripMem<64>{s_pv, s_mv, grp * GL}, s_heads + grp * GL, result[ji], w, recs);
   int bad = 0;
@@ -208,9 +257,9 @@ __global__ __launch_bounds__(64) void nw_trace_group_kernel(const NwJob* __restr
   if (t == 0) status[ji] = static_cast<u32>(rcode);
 }
 
-template <int R, int G>
+template <int R, int G, bool STRIPED = false>
 void launch_sweep(Engine& e, hipStream_t s, const NwJob* d_jobs, const u32* d_idx, u32 n_idx, const ReadsDev& T, const ReadsDev& Rd,
-                  u32* d_hs, NwPm* d_ck, u32* d_result, u32* d_status, u32* d_next) {
+                  u32* d_hs, NwPm* d_ck, u32* d_result, u32* d_status, u32* d_next, int stripe = 0) {
   if (n_idx == 0) return;
   constexpr u32 NG = 64 / G;
   const u32 bundles = (n_idx + NG - 1) / NG;
@@ -219,9 +268,9 @@ void launch_sweep(Engine& e, hipStream_t s, const NwJob* d_jobs, const u32* d_id
   const u32 per_simd = static_cast<u32>(sweep_waves_per_simd<R>());
   const u32 waves = std::min<u32>(bundles, 256u * 4u * (per_simd > 4 ? per_simd - 2 : per_simd));
   RVN_HIP(hipMemsetAsync(d_next, 0, 4, s));
-  RVN_KLAUNCH_ON(kKNwForward, s, (nw_sweep_kernel<R, G><<<(waves + 3) / 4, 256, 0, s>>>(
+  RVN_KLAUNCH_ON(kKNwForward, s, (nw_sweep_kernel<R, G, STRIPED><<<(waves + 3) / 4, 256, 0, s>>>(
                                d_jobs, d_idx, n_idx, T.packed.as<u64>(), Rd.packed.as<u64>(), d_hs, d_ck, d_result,
-                               d_status, d_next)));
+                               d_status, d_next, stripe)));
 }
 
 // largest threshold whose band fits a ring of G lanes with R blocks each
@@ -235,6 +284,7 @@ u32 kcap_of(u32 n, u32 m, u32 R, u32 G) {
 }
 
 u32 level_of(const NwJob& J) {
+  if (J.S) return kStriped;
   for (u32 x = 0; x < kLevels; ++x)
     if (kRs[x] == J.R && kGs[x] == J.G) return x;
   return kLevels - 1;
@@ -250,9 +300,10 @@ u32 level_of(const NwJob& J) {
 // one lane per alignment and latency-bound (~1 us per column), a sweep fills the VALUs — together they cost the time of
 // the sweeps plus the walk of the last, shortest jobs.
 void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vector<NwJob>& jobs, u32 w,
-                    NwWindowRec* d_recs, u64 n_recs, NwStats& st) {
+                    NwWindowRec* d_recs, u64 n_recs, NwStats& st, std::vector<u32>* distances) {
   st = NwStats();
   const u32 nj = static_cast<u32>(jobs.size());
+  if (distances) distances->assign(nj, ~0u);
   hipStream_t s = e.stream;
   RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
   if (nj == 0) return;
@@ -307,13 +358,19 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   } walk_guard{e};
   double rate = e.nw_rate > 0 ? e.nw_rate : 0.13;  // first call: ONT-like; too small only costs a repeat
   if (const char* ev = knob("RVN_NW_RATE")) rate = std::atof(ev);  // (debug builds: force repeats)
+  u64 budget = 0;
+  // engine option nw_stripe_lanes: the widest ring of one sweep (variants with wider rings are skipped) = the stripe size
+  const u32 stripe_lanes = e.opt.nw_stripe_lanes > 0 && e.opt.nw_stripe_lanes < 64 ? static_cast<u32>(e.opt.nw_stripe_lanes) : 64u;
 
-  // plan: the narrowest variant whose ring holds the band of k
+  // plan: the narrowest variant whose ring holds the band of k; beyond the widest, stripes (a band of at most kNwMaxStripes
+  // rings whose stored hs + ck fit the budget; otherwise the job is not aligned)
   auto plan = [&](NwJob& J, u64 k) -> bool {
     const u32 d = J.n > J.m ? J.n - J.m : J.m - J.n;
     k = std::max<u64>(std::max<u64>(k, d), 16);
     k = std::min<u64>(k, static_cast<u64>(J.n) + J.m);  // D(n, m) <= n + m: that threshold never fails
+    J.S = 0;
     for (u32 lvl = 0; lvl < kLevels; ++lvl) {
+      if (kGs[lvl] > stripe_lanes) continue;
       const u32 cap = kcap_of(J.n, J.m, kRs[lvl], kGs[lvl]);
       if (cap >= k) {
         J.R = kRs[lvl];
@@ -323,7 +380,16 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         return true;
       }
     }
-    return false;
+    const u32 cap = kcap_of(J.n, J.m, 8, kNwMaxStripes * stripe_lanes);
+    if (cap < k) return false;
+    const NwGeo g = nw_geo_striped(J.n, J.m, static_cast<u32>(k), 8, stripe_lanes);
+    if (g.hs_words() * 4 + g.ck_entries() * 16 > budget) return false;
+    J.R = 8;
+    J.G = 64;
+    J.S = stripe_lanes;
+    J.k = static_cast<u32>(k);
+    J.kcap = cap;
+    return true;
   };
   std::vector<u32> valid;
   for (u32 i = 0; i < nj; ++i) {
@@ -332,7 +398,6 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     else valid.push_back(i);
   }
 
-  u64 budget = 0;
   {
     size_t free_b = 0, total_b = 0;
     RVN_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -385,7 +450,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   struct Chunk {
     size_t c0, c1;
     u64 hs_w, ck_e;
-    u32 coff[kLevels + 1];
+    u32 coff[kClasses + 1];
   };
   DevBuf* hs_buf[4] = {&e.nw_hs, &e.nw_hs2, &e.nw_hs3, &e.nw_hs4};
   DevBuf* ck_buf[4] = {&e.nw_ck, &e.nw_ck2, &e.nw_ck3, &e.nw_ck4};
@@ -416,8 +481,10 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       parallel_for(nt, 16384, [&](size_t x0, size_t x1) {  // (the GPU waits for this planning: a few host threads)
         for (size_t x = x0; x < x1; ++x) {
           const NwJob& J = jobs[todo[x]];
-          const u32 mm = std::min<u32>(J.m >> 3, (1u << 20) - 1);  // 8-base resolution is plenty for the ordering
-          static_assert(kLevels <= 16, "4 bits of variant + 20 bits of length = the 24 key bits of the two passes");
+          // 8-base resolution is plenty for the ordering; striped jobs by their number of stripes (each stripe launch takes
+          // the jobs that have that stripe: a prefix of the class)
+          const u32 mm = J.S ? std::min<u32>(nw_geo_job(J).n_stripes, (1u << 20) - 1) : std::min<u32>(J.m >> 3, (1u << 20) - 1);
+          static_assert(kClasses <= 16, "4 bits of variant + 20 bits of length = the 24 key bits of the two passes");
           key[x] = 0xFFFFFFu - ((level_of(J) << 20) | mm);
           idx[x] = static_cast<u32>(x);
         }
@@ -446,7 +513,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     parallel_for(order.size(), 16384, [&](size_t x0, size_t x1) {
       for (size_t x = x0; x < x1; ++x) {
         const NwJob& J = jobs[order[x]];
-        const NwGeo g = nw_geo(J.n, J.m, J.k, J.R);
+        const NwGeo g = nw_geo_job(J);
         need[x] = Need{g.hs_words(), g.ck_entries(), static_cast<u64>(J.m) * (static_cast<u64>(g.lo) + g.hi + 1), level_of(J)};
       }
     });
@@ -471,13 +538,13 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         ++c1;
       }
       // the order is by descending level: offsets of the classes inside the chunk, in that order
-      u32 run_off = 0, cnt[kLevels];
-      for (u32 x = 0; x < kLevels; ++x) cnt[x] = C.coff[x + 1];
-      for (int x = static_cast<int>(kLevels) - 1; x >= 0; --x) {
+      u32 run_off = 0, cnt[kClasses];
+      for (u32 x = 0; x < kClasses; ++x) cnt[x] = C.coff[x + 1];
+      for (int x = static_cast<int>(kClasses) - 1; x >= 0; --x) {
         C.coff[x] = run_off;
         run_off += cnt[x];
       }
-      C.coff[kLevels] = run_off;  // count of class x = offset of class x - 1 (or the chunk's end) - its own offset
+      C.coff[kClasses] = run_off;  // count of class x = offset of class x - 1 (or the chunk's end) - its own offset
       C.c1 = c1;
       st.store_bytes = std::max<u64>(st.store_bytes, C.hs_w * 4 + C.ck_e * 16);
       chunks.push_back(C);
@@ -593,6 +660,23 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
             if (side_used[y]) RVN_HIP(hipStreamWaitEvent(e.nw_side[y], e.nw_side_ev[3], 0));
         }
       }
+      if (const u32 n_str = count_of(kStriped)) {
+        // the striped jobs (the widest class: first in the chunk), stripe after stripe on the engine's stream — launch st
+        // takes the jobs that have a stripe st, a prefix of the class (ordered by number of stripes)
+        const u32* idx_s = idx_c + C.coff[kStriped];
+        std::vector<u32> n_stripes(n_str);
+        for (u32 x = 0; x < n_str; ++x) n_stripes[x] = static_cast<u32>(nw_geo_job(jobs[order[C.c0 + C.coff[kStriped] + x]]).n_stripes);
+        for (u32 stp = 0;; ++stp) {
+          u32 n_st = 0;
+          while (n_st < n_str && n_stripes[n_st] > stp) ++n_st;
+          if (n_st == 0) break;
+          launch_sweep<8, 64, true>(e, s, dev.jobs, idx_s, n_st, T, Rd, hs, ck, dev.res, dev.status, d_next, static_cast<int>(stp));
+          if (dbg_sync) {
+            RVN_HIP(hipStreamSynchronize(s));
+            std::fprintf(stderr, "[raven_hip] nw: stripe %u done, %u jobs\n", stp, n_st);
+          }
+        }
+      }
 #define RVN_SWEEP(x, R_, G_)                                                                                         \
   do {                                                                                                               \
     launch_sweep<R_, G_>(e, side[x] ? e.nw_side[(x) % 3] : s, dev.jobs, idx_c + C.coff[x], count_of(x), T, Rd, hs, ck, \
@@ -688,6 +772,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
             const NwJob& J = jobs[i];
             ++n_al;
             sum_d += h_result[i];
+            if (distances) (*distances)[i] = h_result[i];  // (distinct jobs per thread)
             rr.push_back(static_cast<double>(h_result[i]) / std::max(J.n, J.m));
           }
           std::lock_guard<std::mutex> lk(mu_);
@@ -909,6 +994,8 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
 // ---- CPU stepper of the same code (test hook rvn_test_nw_breakpoints): 64 emulated lanes, host arrays --------------
 static u64 g_group_batches_store = 0;
 static u64* const g_group_batches = &g_group_batches_store;  // batches of the hook's last group walk (band[3] when a group walk is asked for)
+static int walk_host(const NwJob& J, const NwGeo& g, const u64* t_words, const u64* r_words, const std::vector<u32>& hs,
+                     const std::vector<NwPm>& ck, u32 res, u32 w, NwWindowRec* recs, u32* band, int walk_gl);
 template <int R>
 static int emulate_job(NwJob J, u32 G, const u64* t_words, const u64* r_words, u32 w, NwWindowRec* recs, u32* distance,
                        u32* band, int walk_gl) {
@@ -966,6 +1053,12 @@ static int emulate_job(NwJob J, u32 G, const u64* t_words, const u64* r_words, u
     band[1] = static_cast<u32>(g.L);
     band[2] = R;
   }
+  return walk_host(J, g, t_words, r_words, hs, ck, res, w, recs, band, walk_gl);
+}
+
+// the walk of an emulated sweep, in the form the hook asks for
+static int walk_host(const NwJob& J, const NwGeo& g, const u64* t_words, const u64* r_words, const std::vector<u32>& hs,
+                     const std::vector<NwPm>& ck, u32 res, u32 w, NwWindowRec* recs, u32* band, int walk_gl) {
   if (walk_gl == 16) return nw_trace_group_host<16>(J, g, t_words, r_words, hs.data(), ck.data(), res, w, recs, band ? g_group_batches : nullptr);
   if (walk_gl == 64) return nw_trace_group_host<64>(J, g, t_words, r_words, hs.data(), ck.data(), res, w, recs, band ? g_group_batches : nullptr);
   if (walk_gl == 4) return nw_trace_group_host<4>(J, g, t_words, r_words, hs.data(), ck.data(), res, w, recs, band ? g_group_batches : nullptr);
@@ -980,6 +1073,98 @@ static int emulate_job(NwJob J, u32 G, const u64* t_words, const u64* r_words, u
   return nw_trace_job<1>(J, g, t_words, r_words, hs.data(), ck.data(), mem, res, w, recs);
 }
 
+// The striped sweep as nw_sweep_kernel<R, 64, true> runs it, stripe after stripe (one launch each), then the walk.
+// band: {k, lanes one ring would need, R, group-walk batches, stripes}
+template <int R>
+static int emulate_striped(NwJob J, u32 S, const u64* t_words, const u64* r_words, u32 w, NwWindowRec* recs, u32* distance,
+                           u32* band, int walk_gl) {
+  std::vector<u64> peq(static_cast<size_t>(R) * 4 * 64);
+  std::vector<NwSweepLane<R, 64, true>> lanes(64);
+  std::vector<int> xp(64), sp(64);
+  std::vector<u32> hs;
+  std::vector<NwPm> ck;
+  NwGeo g;
+  u32 res = 0;
+  J.R = R;
+  J.G = 64;
+  J.S = S;
+  for (;;) {
+    g = nw_geo_job(J);
+    if (nw_ring_lanes(static_cast<u32>(g.lo), static_cast<u32>(g.hi), R) > kNwMaxStripes * S) return -3;  // refused
+    hs.assign(g.hs_words() + 4 * 64 * 8 + 16, 0xA5A5A5A5u);
+    ck.assign(g.ck_entries() + 16, NwPm{0x1234567887654321ULL, 0x0FEDCBA99ABCDEF0ULL});
+    u32 res1 = 0;
+    const u64 row = static_cast<u64>(S) * R;
+    for (int st = 0; st < g.n_stripes; ++st) {
+      NwGeo gs = g;
+      gs.s0 = st * g.S;
+      gs.s1 = std::min(g.n_super, gs.s0 + g.S);
+      const int t0 = g.st_t0(st), g0 = (t0 - 1) >> 4, q0 = (t0 - 1) >> 5;
+      const int n_steps_w = (gs.je(gs.s1 - 1) + gs.s1 + 15) & ~15;
+      const bool last = gs.s1 == g.n_super;
+      int t_hand = kNwNever, lig_hand = -1, sc_hand = 0, sc_in = 0;
+      if (!last && gs.ja(gs.s1) > 1) {
+        t_hand = gs.ja(gs.s1) + gs.s1;
+        lig_hand = gs.s1 - 1 - gs.s0;
+      }
+      NwTopIn top;
+      if (st > 0) {
+        top.init(hs.data(), gs, t0);
+        sc_in = static_cast<int>(hs[g.hand_at(st - 1)]);
+      }
+      u32* hs_j = hs.data() + static_cast<u64>(st) * g.stripe_hs_words();
+      NwPm* ck_j = ck.data() + static_cast<u64>(st) * g.stripe_ck_entries();
+      for (int l = 0; l < 64; ++l) {
+        if (l < static_cast<int>(S)) lanes[l].init(J, t_words, r_words, gs, l, peq.data(), l);
+        else lanes[l].init_idle(peq.data(), l);
+      }
+      for (int t = t0; t <= n_steps_w; ++t) {
+        for (int l = 0; l < 64; ++l) {
+          const int src = l == 0 ? g.L - 1 : l - 1;
+          xp[l] = lanes[src].xf;
+          sp[l] = lanes[src].sc;
+        }
+        if (st > 0) {
+          xp[0] = top.x(t);
+          sp[0] = sc_in;
+        }
+        if (t == t_hand) sc_hand = lanes[lig_hand].sc;
+        for (int l = 0; l < 64; ++l)
+          if (lanes[l].has_event(t)) lanes[l].event(t, xp[l], sp[l]);
+        for (int l = 0; l < 64; ++l) lanes[l].step(t, xp[l]);
+        if ((t & 15) == 0) {
+          const int gi = (t >> 4) - 1;
+          for (int l = 0; l < g.L; ++l) {
+            if (gi - g0 < g.gps)
+              for (int r = 0; r < R; ++r) hs_j[static_cast<u64>(gi - g0) * row + static_cast<u64>(l) * R + r] = lanes[l].acc[r];
+            if ((t & 31) == 0 && (t >> 5) - 1 - q0 < g.qps)
+              for (int r = 0; r < R; ++r)
+                ck_j[static_cast<u64>((t >> 5) - 1 - q0) * row + static_cast<u64>(l) * R + r] = NwPm{lanes[l].Pv[r], lanes[l].Mv[r]};
+          }
+          for (int l = 0; l < 64; ++l) lanes[l].next_group(t);
+          if (st > 0) top.next_group(t);
+        }
+      }
+      if (lig_hand >= 0) hs_j[row * static_cast<u64>(g.gps)] = static_cast<u32>(sc_hand);
+      if (last)
+        for (int l = 0; l < 64; ++l) res1 = std::max(res1, lanes[l].result);
+    }
+    if (res1 == 0) return -5;
+    res = res1 - 1u;
+    if (res <= J.k) break;
+    if (J.k >= J.n + J.m) return -5;
+    J.k = static_cast<u32>(std::min<u64>(2ULL * J.k, static_cast<u64>(J.n) + J.m));
+  }
+  *distance = res;
+  if (band) {
+    band[0] = J.k;
+    band[1] = nw_ring_lanes(static_cast<u32>(g.lo), static_cast<u32>(g.hi), R);
+    band[2] = R;
+    band[4] = static_cast<u32>(g.n_stripes);
+  }
+  return walk_host(J, g, t_words, r_words, hs, ck, res, w, recs, band, walk_gl);
+}
+
 // force_R > 0: that many blocks per lane (whole-wave ring); force_R < 0: R = 1 with a ring of at most -force_R lanes
 // (the lane groups of the narrow variants); force_R >= 1000: the variant (R, G) = (force_R / 1000, force_R % 1000);
 // 0: the narrowest variant that holds k, the next one on overflow
@@ -987,6 +1172,7 @@ int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r
                         u32 m, int rc, u32 w, u32 k, int force_R, NwWindowRec* recs, u32* distance, u32* band) {
   (void)t_len;
   const int walk_gl = (rc >> 8) & 0xFF;  // bits 8-15 of rc: lanes per alignment of the group walk (0: the lane walk)
+  const u32 stripe_lanes = static_cast<u32>(rc >> 16) & 0xFFu;  // bits 16-23: lanes per stripe of a striped sweep (0: none)
   rc &= 1;
   g_group_batches_store = 0;
   if (n == 0 || m == 0) return -1;
@@ -1004,6 +1190,21 @@ int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r
   }
   const u32 d = n > m ? n - m : m - n;
   u64 kk = std::min<u64>(std::max<u64>(std::max<u64>(k, d), 1), static_cast<u64>(n) + m);
+  if (stripe_lanes) {  // striped, whatever the band: R = force_R (1 / 2 / 4 / 8; default 1)
+    if (stripe_lanes > 64) return -2;
+    J.k = static_cast<u32>(kk);
+    int rcode;
+    switch (force_R) {
+      case 0:
+      case 1: rcode = emulate_striped<1>(J, stripe_lanes, t_words, r_words, w, recs, distance, band, walk_gl); break;
+      case 2: rcode = emulate_striped<2>(J, stripe_lanes, t_words, r_words, w, recs, distance, band, walk_gl); break;
+      case 4: rcode = emulate_striped<4>(J, stripe_lanes, t_words, r_words, w, recs, distance, band, walk_gl); break;
+      case 8: rcode = emulate_striped<8>(J, stripe_lanes, t_words, r_words, w, recs, distance, band, walk_gl); break;
+      default: return -2;
+    }
+    if (walk_gl && band && rcode >= 0) band[3] = static_cast<u32>(g_group_batches_store);
+    return rcode;
+  }
   u32 lvl = 0;
   if (force_R >= 1000) {  // R * 1000 + G: one particular variant
     while (lvl < kLevels && !(kRs[lvl] == static_cast<u32>(force_R / 1000) && kGs[lvl] == static_cast<u32>(force_R % 1000))) ++lvl;

@@ -25,7 +25,9 @@ namespace rvn {
 
 constexpr int kNwNever = 0x7FFFFFFF;
 
-template <int R, int LANES>
+// STRIPED: the lane sweeps one stripe of a striped band (NwGeo: super-blocks g.s0 .. g.s1 - 1, one per lane; the top
+// input of the stripe's first lane comes from NwTopIn, not from the ring)
+template <int R, int LANES, bool STRIPED = false>
 struct NwSweepLane {
   // job
   const u64* a_words;  // target words of the job
@@ -63,9 +65,9 @@ struct NwSweepLane {
     lig = lig_;
     peq = peq_;
     lane = lane_;
-    s = lig_ < geo.L ? lig_ : geo.n_super;
+    s = lig_ < geo.L ? (STRIPED ? geo.s0 + lig_ : lig_) : s_end();
     active = false;
-    t_evt = (s < g.n_super && g.ja(s) <= g.m) ? g.ja(s) + s : kNwNever;
+    t_evt = (s < s_end() && g.ja(s) <= g.m) ? g.ja(s) + s : kNwNever;
     t_fed = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -130,6 +132,7 @@ struct NwSweepLane {
     for (int r = 0; r < R; ++r) eq[r] = peq[(r * 4 + static_cast<int>(c)) * LANES + lane];
   }
 
+  __host__ __device__ int s_end() const { return STRIPED ? g.s1 : g.n_super; }
   __host__ __device__ bool has_event(int t) const { return t == t_evt; }
 
   // x_prev / sc_prev: xf and sc of the ring's previous lane after step t - 1
@@ -149,7 +152,7 @@ struct NwSweepLane {
       }
       s += g.L;
       active = false;
-      t_evt = (s < g.n_super && g.ja(s) <= g.m) ? g.ja(s) + s : kNwNever;
+      t_evt = (s < s_end() && g.ja(s) <= g.m) ? g.ja(s) + s : kNwNever;
     }
     if (!active && t == t_evt) {  // super-block s enters the band at column t - s
       const int ja = t - s;
@@ -196,6 +199,35 @@ struct NwSweepLane {
     w_cur = w_nxt;
     w_nxt = window_finish((t >> 4) + 1);  // t = 16 (gi + 1): the group after the one that starts now; loaded 16 steps ago
     window_load((t >> 4) + 2);
+  }
+};
+
+// The top boundary of stripe st > 0 of a striped sweep: what the ring's previous lane would hand its first lane at step t
+// (the horizontal delta out of super-block s0 - 1's last block at step t - 1), read from stripe st - 1's hs stream.
+// Two words of it in a register (the bits of steps 16 G - 15 .. 16 G + 16 while the loop is in group G + 1 .. ), the next
+// one loaded a whole group ahead; group indices outside stripe st - 1's region are clamped (NwGeo::hs_at), and are only
+// read where the lane does not use them (before its super-block enters, after the one above retired).
+struct NwTopIn {
+  const u32* hs;  // the job's hs region
+  NwGeo g;
+  int s_above;    // the last super-block of the stripe above
+  u64 win;
+  u32 nxt;
+  __host__ __device__ u32 word(int gi) const { return hs[g.hs_at(s_above, g.R - 1, gi)]; }
+  // t0 = first step of the loop (1 mod 16)
+  __host__ __device__ void init(const u32* hs_, const NwGeo& g_, int t0) {
+    hs = hs_;
+    g = g_;
+    s_above = g_.s0 - 1;
+    const int G = (t0 - 1) >> 4;
+    win = static_cast<u64>(word(G - 1)) | (static_cast<u64>(word(G)) << 32);
+    nxt = word(G + 1);
+  }
+  __host__ __device__ int x(int t) const { return static_cast<int>(win >> (2 * ((t - 1) & 15) + 30)) & 3; }
+  // after step t = 16 G
+  __host__ __device__ void next_group(int t) {
+    win = (win >> 32) | (static_cast<u64>(nxt) << 32);
+    nxt = word((t >> 4) + 1);
   }
 };
 

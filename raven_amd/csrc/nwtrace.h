@@ -75,12 +75,11 @@ struct NwStripCells {
   }
 };
 
-// 2 x 32 bits of the hs stream of (ring lane `lane`, block r of the lane) for the steps u_first .. u_first + 31 (0-based),
-// the bits of step u_first in bits 0-1
-__host__ __device__ inline u64 nw_hs_bits(const u32* __restrict__ hs, const NwGeo& g, int lane, int r, int u_first) {
+// 2 x 32 bits of the hs stream of (super-block s, block r of it) for the steps u_first .. u_first + 31 (0-based), the
+// bits of step u_first in bits 0-1 (NwGeo::hs_at: the ring lane of s, or its stripe's region of a striped band)
+__host__ __device__ inline u64 nw_hs_bits(const u32* __restrict__ hs, const NwGeo& g, int s, int r, int u_first) {
   const u64 stride = static_cast<u64>(g.L) * static_cast<u64>(g.R);
-  const u64 g0 = static_cast<u64>(u_first) >> 4;
-  const u32* p = hs + g0 * stride + static_cast<u64>(lane) * static_cast<u64>(g.R) + static_cast<u64>(r);
+  const u32* p = hs + g.hs_at(s, r, u_first >> 4);
   const unsigned sh = 2u * (static_cast<unsigned>(u_first) & 15u);
   const u32 x0 = p[0], x1 = p[stride], x2 = p[2 * stride];  // all three at once (the buffer has slack behind the last job)
   const u64 lo = static_cast<u64>(x0) | (static_cast<u64>(x1) << 32);
@@ -107,10 +106,10 @@ __host__ __device__ inline int nw_trace_job(const NwJob& J, const NwGeo& g, cons
   NwWalkerT<NwStripCells<LANES>> wk;
   wk.cells.mem = mem;
   wk.init(J, distance, w, recs_all);
-  const int R = g.R, L = g.L;
+  const int R = g.R;
   while (wk.i > 0 && wk.j > 0) {
     const int b = (wk.i - 1) >> 6;
-    const int s = b / R, r = b - s * R, p = s % L;
+    const int s = b / R, r = b - s * R;
     const int j = wk.j;
     const int ja = g.ja(s), je = g.je(s);
     if (s >= g.n_super || j < ja || j > je) return 1;  // the walk left the band: cannot happen for a result <= k
@@ -122,7 +121,7 @@ __host__ __device__ inline int nw_trace_job(const NwJob& J, const NwGeo& g, cons
     int j0;
     if (q >= 0 && jc >= ja) {
       j0 = jc;
-      const NwPm v = ck[(static_cast<u64>(q) * static_cast<u64>(L) + static_cast<u64>(p)) * static_cast<u64>(R) + static_cast<u64>(r)];
+      const NwPm v = ck[g.ck_at(s, r, q)];
       pv = v.pv;
       mv = v.mv;
     } else {
@@ -134,9 +133,9 @@ __host__ __device__ inline int nw_trace_job(const NwJob& J, const NwGeo& g, cons
     // horizontal input at columns j0 + 1 ..: the block above — same lane (r > 0) or the ring's previous lane one step earlier
     u64 hinw;
     if (r > 0) {
-      hinw = nw_hs_bits(hs, g, p, r - 1, j0 + s);
+      hinw = nw_hs_bits(hs, g, s, r - 1, j0 + s);
     } else if (s > 0 && j0 + 1 <= g.jfed(s)) {
-      hinw = nw_hs_bits(hs, g, p == 0 ? L - 1 : p - 1, R - 1, j0 + s - 1);
+      hinw = nw_hs_bits(hs, g, s - 1, R - 1, j0 + s - 1);
       const int nfed = g.jfed(s) - j0;  // columns that are still fed
       if (nfed < 32) hinw = (hinw & ((1ULL << (2 * nfed)) - 1ULL)) | (0x5555555555555555ULL << (2 * nfed));
     } else {
@@ -270,7 +269,7 @@ __host__ __device__ inline void nw_fill_strip(const NwJob& J, const NwGeo& g, co
                                               const u64* __restrict__ rw, long long b_first, bool rc,
                                               const u32* __restrict__ hs, const NwPm* __restrict__ ck, const NwStripKey& key,
                                               const NwStripMem<LANES>& mem, NwStripHead* head) {
-  const int R = g.R, L = g.L;
+  const int R = g.R;
   const int b = key.b, q = key.q;
   NwStripHead h;
   h.b = -1;
@@ -279,7 +278,7 @@ __host__ __device__ inline void nw_fill_strip(const NwJob& J, const NwGeo& g, co
   h.len = 0;
   h.hinw = h.tlo = h.thi = 0;
   h.rlo = h.rhi = 0;
-  const int s = b >= 0 ? b / R : 0, r = b - s * R, p = s % L;
+  const int s = b >= 0 ? b / R : 0, r = b - s * R;
   const int ja = g.ja(s), je = g.je(s);
   const int jc = 32 * (q + 1) - s;
   const bool from_ck = q >= 0 && jc >= ja;  // (as nw_trace_job: the checkpoint, or the column before the block enters the band)
@@ -292,7 +291,7 @@ __host__ __device__ inline void nw_fill_strip(const NwJob& J, const NwGeo& g, co
   }
   u64 pv, mv;
   if (from_ck) {
-    const NwPm v = ck[(static_cast<u64>(q) * static_cast<u64>(L) + static_cast<u64>(p)) * static_cast<u64>(R) + static_cast<u64>(r)];
+    const NwPm v = ck[g.ck_at(s, r, q)];
     pv = v.pv;
     mv = v.mv;
   } else {
@@ -302,9 +301,9 @@ __host__ __device__ inline void nw_fill_strip(const NwJob& J, const NwGeo& g, co
   const int len = jr - j0;  // 1 .. 32
   u64 hinw;
   if (r > 0) {
-    hinw = nw_hs_bits(hs, g, p, r - 1, j0 + s);
+    hinw = nw_hs_bits(hs, g, s, r - 1, j0 + s);
   } else if (s > 0 && j0 + 1 <= g.jfed(s)) {
-    hinw = nw_hs_bits(hs, g, p == 0 ? L - 1 : p - 1, R - 1, j0 + s - 1);
+    hinw = nw_hs_bits(hs, g, s - 1, R - 1, j0 + s - 1);
     const int nfed = g.jfed(s) - j0;
     if (nfed < 32) hinw = (hinw & ((1ULL << (2 * nfed)) - 1ULL)) | (0x5555555555555555ULL << (2 * nfed));
   } else {

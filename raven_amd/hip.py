@@ -1047,19 +1047,28 @@ NW_REC_DTYPE = np.dtype([("first_t", "<u4"), ("first_q", "<u4"), ("last_t", "<u4
                          ("grid", "<u2", (8,))])
 
 
-def test_nw_breakpoints(t_words, t_len, r_words, r_len, t_begin, n, q_begin, m, rc, w, k=64, force_r=0, group_lanes=0):
+def test_nw_breakpoints(t_words, t_len, r_words, r_len, t_begin, n, q_begin, m, rc, w, k=64, force_r=0, group_lanes=0,
+                       stripe_lanes=0, device=False):
     """nwpath.h stepped on the CPU (no GPU needed): the forward sweep's lane code for 64 emulated lanes + the
-    traceback (group_lanes = 4 / 16 / 64: the walk by a group of lanes per alignment, nwtrace.h).  Returns (records per
-    window, exact distance, (k, lanes, R[, batches of the group walk]), status)."""
+    traceback (group_lanes = 4 / 16 / 64: the walk by a group of lanes per alignment, nwtrace.h).  stripe_lanes > 0: the
+    striped sweep, stripes of that many lanes (R = force_r, default 1; a band wider than 8 such rings is refused).  Returns
+    (records per window, exact distance, band, status) with band = (k, lanes, R), (k, lanes, R, batches of the group
+    walk) with group_lanes, and always the five entries (k, lanes, R, batches or 0, stripes) with stripe_lanes.
+    device=True: the production stage on the GPU instead (an engine of its own; stripe_lanes = engine option
+    nw_stripe_lanes, k / force_r / group_lanes unused); band is then a dict {k, stripe_lanes (0: one ring), R, stripes,
+    stage_ms} of the job's final plan."""
     t_words = np.ascontiguousarray(t_words, dtype=np.uint64)
     r_words = np.ascontiguousarray(r_words, dtype=np.uint64)
     n_win = (t_begin + n - 1) // w - t_begin // w + 1
     recs = np.zeros(n_win, dtype=NW_REC_DTYPE)
     dist = np.zeros(1, dtype=np.uint32)
-    band = np.zeros(4 if group_lanes else 3, dtype=np.uint32)
-    rc_ = test_lib().rvn_test_nw_breakpoints(_p(t_words), t_len, _p(r_words), r_len, t_begin, n, q_begin, m,
-                                        (1 if rc else 0) | (int(group_lanes) << 8), w, k,
-                                        force_r, _p(recs), _p(dist), _p(band))
+    band = np.zeros(5 if (stripe_lanes or device) else (4 if group_lanes else 3), dtype=np.uint32)
+    flags = (1 if rc else 0) | (int(stripe_lanes) << 16) | (1 << 24 if device else int(group_lanes) << 8)
+    rc_ = test_lib().rvn_test_nw_breakpoints(_p(t_words), t_len, _p(r_words), r_len, t_begin, n, q_begin, m, flags, w, k,
+                                             force_r, _p(recs), _p(dist), _p(band))
     if rc_ < 0:
         raise ValueError("rvn_test_nw_breakpoints: %d" % rc_)
+    if device:
+        return recs, int(dist[0]), dict(k=int(band[0]), stripe_lanes=int(band[1]), R=int(band[2]), stripes=int(band[3]),
+                                        stage_ms=band[4] / 1000.0), rc_
     return recs, int(dist[0]), tuple(int(x) for x in band), rc_
