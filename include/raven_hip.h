@@ -424,6 +424,27 @@ int rvn_group_polish_round_q(rvn_group* g, const uint64_t* t_packed, const uint6
  * some pair is not, RVN_EINVAL for a NULL group. */
 int rvn_group_peer_access(const rvn_group* g, uint8_t* direct);
 
+/* The rest of the overlap phase of raven::ConstructGraph (construct.cc:650-707) over the group; host arrays in, the reads
+ * as rvn_group_find_overlaps_and_create_piles takes them (read i = id i).
+ *   rvn_group_find_overlaps_and_repetitive_regions  = rvn_find_overlaps_and_repetitive_regions over all devices: ONE result
+ *       handle, owned by rank 0's engine, byte-identical to the single engine's on the same input (fetch and release it
+ *       with rvn_pass2_*).  The valid reads are split into contiguous ranges balanced by length x index batches mapped
+ *       against; every rank builds the index of each batch that ends after the start of its range (the whole batch:
+ *       replicated, not divided) and maps the valid reads of its range (Map, AddKmers, identity filter, classification); rank 0
+ *       gathers the survivors in batch-major, rank-minor order, the k-mer cells of every range and the containment flags
+ *       OR'd over the ranks, then runs the de-duplication, invalidation and final OverlapUpdate sweep once.
+ *   rvn_group_filter_overlaps_by_identity           = rvn_filter_overlaps_by_identity over all devices: piles split
+ *       into contiguous ranges balanced by the span lengths of their overlaps, lists updated in place exactly as the
+ *       single-engine call does. */
+int rvn_group_find_overlaps_and_repetitive_regions(rvn_group* g, const uint64_t* packed, const uint64_t* word_offsets,
+                                                   const uint32_t* lengths, uint32_t n_reads, const uint32_t* pile_begin,
+                                                   const uint32_t* pile_end, const uint8_t* pile_invalid, double freq,
+                                                   uint32_t kmer_len, double identity, uint64_t batch_bases, rvn_pass2** out);
+int rvn_group_filter_overlaps_by_identity(rvn_group* g, const uint64_t* packed, const uint64_t* word_offsets,
+                                          const uint32_t* lengths, uint32_t n_reads, rvn_overlap* overlaps, uint32_t* offsets,
+                                          const uint32_t* pile_begin, const uint32_t* pile_end, const uint8_t* pile_invalid,
+                                          double identity);
+
 /* raven::OverlapUpdate (RavenLib/src/overlap_utils.cc:14-85) followed by raven::GetOverlapType (:87-121) on a list of
  * overlaps, on the HOST (the library's __host__ build of the rules its kernels run: raven_amd/csrc/overlap_rules.h) — for
  * a caller that holds overlaps and pile regions in host arrays between two device stages, as ResolveContainedReads does

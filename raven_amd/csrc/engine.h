@@ -378,8 +378,30 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
 void reads_subset(Engine& e, const ReadsDev& R, const std::vector<u32>& src, ReadsDev& V);
 void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid, double freq,
                  u32 kmer_len, double identity, u64 batch_bases, Pass2State& out);
+// The stages of second_pass, also driven per rank by the device group (group.hip)
+struct PileRegion;
+struct Pass2Prep {
+  std::vector<u32> valid;                       // ids of the valid reads, ascending
+  u32 sv = 0;                                   // valid reads that are mapped (0: every pile valid, construct.cc:343-349)
+  ReadsDev V;                                   // the valid reads (ids = original ids)
+  std::vector<u64> h_v_kmers_off;               // first k-mer cell of valid read i (+ the total)
+  std::vector<std::pair<u32, u32>> batches;     // index batches [first, last) of the valid reads
+  PileRegion* d_regions = nullptr;              // engine scratch: pile regions by id
+  u32* d_index_of = nullptr;                    // engine scratch: id -> index among the valid reads
+  u64* d_v_kmers_off = nullptr;
+};
+void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid,
+                         u64 batch_bases, Pass2State& out, Pass2Prep& P);
+u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first, u32 q_last, double freq, u32 kmer_len,
+                      double identity, Pass2State& out);
+void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out);
+void or_bytes(Engine& e, u8* d_dst, const u8* d_src, u64 n);  // d_dst[i] |= d_src[i]
 void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_off, const u32* h_begin, const u32* h_end,
                            const u8* h_invalid, double identity);
+// its two halves: the device part on a flat list (ok flags + updated overlaps out) and the per-pile compaction
+void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u64 O, const u32* h_begin, const u32* h_end,
+                           const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd);
+void identity_filter_compact(Overlap* h_ovl, u32* h_off, u32 n, const u8* ok, const Overlap* upd);
 
 // Pass-1 state: per-pile kept overlaps + coverage (pile.hip)
 struct PileState {
@@ -406,3 +428,17 @@ void pile_add_kmers_batch(Engine& e, const ReadsDev& r, const u32* h_pos, const 
 void pile_add_layers_single(Engine& e, PileState& ps, const u32* d_ids, const Overlap* h_ovl, u32 n);
 
 }  // namespace rvn
+
+// Handles of the C ABI (include/raven_hip.h) that engine.hip and group.hip both look into
+struct rvn_engine {
+  rvn::Engine e;
+};
+struct rvn_reads {
+  rvn::ReadsDev r;
+  std::vector<std::string> names;  // rvn_reads_load: the sequences' names
+};
+struct rvn_pass2 {
+  rvn::Engine* e = nullptr;
+  rvn::Pass2State st;
+  std::weak_ptr<int> engine_life;
+};

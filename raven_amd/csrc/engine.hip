@@ -29,13 +29,6 @@ using namespace rvn;
 
 static_assert(sizeof(rvn_overlap) == sizeof(rvn::Overlap), "overlap layout");
 
-struct rvn_engine {
-  Engine e;
-};
-struct rvn_reads {
-  ReadsDev r;
-  std::vector<std::string> names;  // rvn_reads_load: the sequences' names
-};
 // The pile buffers (coverage, kept lists, merge scratch: a dozen allocations) are recycled through the engine:
 // destroying a pass hands them back, the next pass adopts them, so steady-state passes do not touch the allocator.
 struct rvn_pass1 {
@@ -415,12 +408,6 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
   do_minimize(e, r, first, last, minhash);
 }
 }  // namespace rvn
-
-struct rvn_pass2 {
-  Engine* e = nullptr;
-  Pass2State st;
-  std::weak_ptr<int> engine_life;
-};
 
 extern "C" {
 

@@ -471,6 +471,162 @@ void polish_rank(Rank& R, const PolishArgs& A) {
   }
 }
 
+// contiguous ranges of n items balanced by 64-bit weights (cut where the running sum reaches r / world of the total)
+std::vector<u32> partition_weights(const std::vector<u64>& wgt, u32 world) {
+  const u32 n = static_cast<u32>(wgt.size());
+  std::vector<u64> cum(static_cast<size_t>(n) + 1, 0);
+  for (u32 i = 0; i < n; ++i) cum[i + 1] = cum[i] + wgt[i];
+  std::vector<u32> b(world + 1, 0);
+  b[world] = n;
+  for (u32 h = 1; h < world; ++h) {
+    const double target = static_cast<double>(cum[n]) * h / world;
+    b[h] = static_cast<u32>(std::lower_bound(cum.begin(), cum.end(), target,
+                                             [](u64 c, double t) { return static_cast<double>(c) < t; }) - cum.begin());
+  }
+  for (u32 h = 1; h <= world; ++h) b[h] = std::max(b[h], b[h - 1]);
+  return b;
+}
+
+// Second pass (FindOverlapsAndRepetetiveRegions, construct.cc:316-491) over the group.  Every rank holds every read and
+// builds the index of every batch that ends after the first valid read of its range (Minimize + Filter of the WHOLE batch:
+// the same occurrence threshold everywhere; batches that end before its range are skipped), and maps only the valid reads
+// of ITS range: Map output, the `filtered` flags and with them Pile::AddKmers, the identity filter and the classification
+// of an overlap all belong to its query read, so the ranks need no exchange until the end.  The ranges are balanced by
+// length x batches mapped against, the mapping work; the index builds are repeated, not divided.  Then
+// rank 0 gathers (peer copies into one rvn_pass2 on its engine): the survivors in batch-major, rank-minor order (= the
+// reference's serial merge order, each rank's list being in query-read order), the k-mer cells of every rank's range, the
+// containment flags OR'd over the ranks; and runs the de-duplication, invalidation and final OverlapUpdate sweep once.
+struct Pass2Args {
+  const uint64_t* packed;
+  const uint64_t* word_offsets;
+  const uint32_t* lengths;
+  u32 n;
+  const uint32_t *begin, *end;
+  const uint8_t* invalid;
+  double freq;
+  u32 kmer_len;
+  double identity;
+  u64 batch_bases;
+  const std::vector<u32>* vbounds;           // ranges of the VALID reads (indices into the valid list), world + 1
+  std::vector<const rvn::Pass2State*>* loc;  // every rank's partial result (published for rank 0)
+  std::vector<std::vector<u64>>* per_batch;  // survivors of every rank per index batch
+  rvn_pass2* result;                         // rank 0's engine
+};
+
+void pass2_rank(Rank& R, const Pass2Args& A) {
+  rvn_group& G = R.g;
+  const u32 world = G.world(), g = R.r;
+  R.hip(hipSetDevice(G.dev[g]), "hipSetDevice");
+  rvn::Engine& e = R.e->e;
+  rvn_reads* all = nullptr;
+  R.check(rvn_reads_upload(R.e, A.packed, A.word_offsets[A.n], A.word_offsets, A.lengths, nullptr, A.n, &all));
+  struct Guard {
+    rvn_reads* p;
+    ~Guard() { rvn_reads_destroy(p); }
+  } guard{all};
+  rvn::engine_release_scratch_if_tight(e, 1);
+  rvn::Pass2State loc;
+  rvn::Pass2Prep P;
+  rvn::second_pass_prepare(e, all->r, A.begin, A.end, A.invalid, A.batch_bases, loc, P);
+  const u32 q_lo = (*A.vbounds)[g], q_hi = std::min((*A.vbounds)[g + 1], P.sv);
+  std::vector<u64>& mine = (*A.per_batch)[g];
+  mine.assign(P.batches.size(), 0);
+  for (size_t b = 0; b < P.batches.size(); ++b) {
+    const u32 first = P.batches[b].first, last = P.batches[b].second;
+    const u32 qf = std::min(q_lo, last), ql = std::min(q_hi, last);
+    mine[b] = rvn::second_pass_batch(e, P, first, last, qf, ql, A.freq, A.kmer_len, A.identity, loc);
+  }
+  // The batches' last kernels (the append into loc.ovl, AddKmers into loc.kmers) are asynchronous on e.stream, which
+  // rank 0's peer copies on its copy stream are not ordered with: the partial result is complete only after this sync.
+  R.hip(hipStreamSynchronize(e.stream), "second pass");
+  (*A.loc)[g] = &loc;
+  R.barrier();  // every partial result is complete
+  if (g == 0) {
+    rvn::Pass2State& out = A.result->st;
+    out.n = loc.n;
+    out.h_kmers_off = loc.h_kmers_off;
+    out.kmers_total = loc.kmers_total;
+    u64 total = 0;
+    for (u32 s = 0; s < world; ++s)
+      for (u64 c : (*A.per_batch)[s]) total += c;
+    rvn::Overlap* d_ovl = out.ovl.get<rvn::Overlap>(total + 1);
+    u8* d_kmers = out.kmers.get<u8>(out.kmers_total + 16);
+    u8* d_contained = out.contained.get<u8>(static_cast<size_t>(out.n) + 16);
+    DevBuf other;
+    u8* d_other = other.get<u8>(static_cast<size_t>(out.n) + 16);
+    R.hip(hipMemsetAsync(d_kmers, 0, out.kmers_total + 16, R.cs), "memset");
+    // overlaps: batch-major, rank-minor
+    std::vector<u64> src_at(world, 0);
+    u64 at = 0;
+    for (size_t b = 0; b < P.batches.size(); ++b)
+      for (u32 s = 0; s < world; ++s) {
+        const u64 c = (*A.per_batch)[s][b];
+        if (c)
+          R.hip(hipMemcpyPeerAsync(d_ovl + at, G.dev[0], (*A.loc)[s]->ovl.as<rvn::Overlap>() + src_at[s], G.dev[s],
+                                   c * sizeof(rvn::Overlap), R.cs), "peer copy");
+        at += c;
+        src_at[s] += c;
+      }
+    // k-mer cells: every rank filled those of its own valid reads only
+    for (u32 s = 0; s < world && P.sv; ++s) {
+      const u64 k0 = P.h_v_kmers_off[(*A.vbounds)[s]], k1 = P.h_v_kmers_off[(*A.vbounds)[s + 1]];
+      if (k1 > k0)
+        R.hip(hipMemcpyPeerAsync(d_kmers + k0, G.dev[0], (*A.loc)[s]->kmers.as<u8>() + k0, G.dev[s], k1 - k0, R.cs),
+              "peer copy");
+    }
+    if (out.n) R.hip(hipMemcpyAsync(d_contained, loc.contained.ptr, out.n, hipMemcpyDeviceToDevice, R.cs), "copy");
+    R.hip(hipStreamSynchronize(R.cs), "peer copy");
+    for (u32 s = 1; s < world && out.n; ++s) {  // containment flags name reads of any rank: OR over the ranks
+      R.hip(hipMemcpyPeerAsync(d_other, G.dev[0], (*A.loc)[s]->contained.ptr, G.dev[s], out.n, R.cs), "peer copy");
+      R.hip(hipStreamSynchronize(R.cs), "peer copy");
+      rvn::or_bytes(e, d_contained, d_other, out.n);
+    }
+    out.n_overlaps = total;
+    if (P.sv) rvn::second_pass_finish(e, P.d_regions, out);
+  }
+  R.barrier();  // rank 0 has pulled: the partial results may go
+}
+
+// Identity filter of ResolveContainedReads (construct.cc:162-217) over the group: piles in contiguous ranges, each rank
+// scores the lists of its range (flags + updated overlaps into the caller's host arrays at the range's place).
+struct IdentityArgs {
+  const uint64_t* packed;
+  const uint64_t* word_offsets;
+  const uint32_t* lengths;
+  u32 n;
+  const rvn::Overlap* ovl;
+  const uint32_t* offsets;
+  const uint32_t *begin, *end;
+  const uint8_t* invalid;
+  double identity;
+  const std::vector<u32>* bounds;  // pile ranges
+  u8* ok;
+  rvn::Overlap* upd;
+};
+
+void identity_rank(Rank& R, const IdentityArgs& A) {
+  const u32 g = R.r;
+  const u64 o0 = A.offsets[(*A.bounds)[g]], o1 = A.offsets[(*A.bounds)[g + 1]];
+  if (o1 == o0) return;
+  R.hip(hipSetDevice(R.g.dev[g]), "hipSetDevice");
+  rvn_reads* all = nullptr;
+  R.check(rvn_reads_upload(R.e, A.packed, A.word_offsets[A.n], A.word_offsets, A.lengths, nullptr, A.n, &all));
+  struct Guard {
+    rvn_reads* p;
+    ~Guard() { rvn_reads_destroy(p); }
+  } guard{all};
+  rvn::identity_filter_flags(R.e->e, all->r, A.ovl + o0, o1 - o0, A.begin, A.end, A.invalid, A.identity, A.ok + o0,
+                             A.upd + o0);
+}
+
+// the read arrays of a group call, checked before any worker thread starts (rvn_reads_upload's rule)
+bool reads_consistent(const uint64_t* word_offsets, const uint32_t* lengths, u32 n) {
+  for (u32 i = 0; i < n; ++i)
+    if (word_offsets[i + 1] < word_offsets[i] || word_offsets[i + 1] - word_offsets[i] < (static_cast<u64>(lengths[i]) + 31) / 32)
+      return false;
+  return n < rvn::kMaxReadId;
+}
+
 template <class F>
 int run_ranks(rvn_group* g, F fn) {
   g->failed.store(false);
@@ -632,6 +788,110 @@ int rvn_group_polish_round(rvn_group* g, const uint64_t* t_packed, const uint64_
                            double* ratio) {
   return rvn_group_polish_round_q(g, t_packed, t_word_offsets, t_lengths, n_targets, r_packed, r_word_offsets, r_lengths, n_reads,
                                   nullptr, nullptr, 0, q, err, w, trim, match, mismatch, gap, out_codes, out_offsets, out_len, ratio);
+}
+
+int rvn_group_find_overlaps_and_repetitive_regions(rvn_group* g, const uint64_t* packed, const uint64_t* word_offsets,
+                                                   const uint32_t* lengths, uint32_t n_reads, const uint32_t* pile_begin,
+                                                   const uint32_t* pile_end, const uint8_t* pile_invalid, double freq,
+                                                   uint32_t kmer_len, double identity, uint64_t batch_bases, rvn_pass2** out) {
+  if (!g || !out || (n_reads && (!packed || !word_offsets || !lengths || !pile_begin || !pile_end || !pile_invalid))) {
+    rvn::set_last_error("[raven_hip] rvn_group_find_overlaps_and_repetitive_regions: NULL argument");
+    return RVN_EINVAL;
+  }
+  *out = nullptr;
+  if (!(0 <= freq && freq <= 1)) {
+    rvn::set_last_error("[ram::MinimizerEngine::Filter] error: invalid frequency");
+    return RVN_EINVAL;
+  }
+  if (kmer_len == 0 || kmer_len > 32 || batch_bases == 0) {
+    rvn::set_last_error("[raven_hip] rvn_group_find_overlaps_and_repetitive_regions: kmer_len must be in [1, 32], "
+                        "batch_bases positive");
+    return RVN_EINVAL;
+  }
+  if (!reads_consistent(word_offsets, lengths, n_reads)) {
+    rvn::set_last_error("[raven_hip] rvn_group_find_overlaps_and_repetitive_regions: word_offsets inconsistent with lengths");
+    return RVN_EINVAL;
+  }
+  std::unique_ptr<rvn_pass2> p(new rvn_pass2());
+  p->e = &g->eng[0]->e;
+  p->engine_life = p->e->life;
+  if (n_reads == 0) {  // what the single engine returns for an empty read set
+    p->st.h_kmers_off.assign(1, 0);
+    *out = p.release();
+    return RVN_OK;
+  }
+  // valid reads in contiguous ranges balanced by the mapping work: a valid read is mapped against its own index batch
+  // and every later one (construct.cc:362-383), so it weighs its length times that number of batches (the batches as
+  // second_pass_prepare cuts them)
+  std::vector<u64> vlen;
+  for (u32 i = 0; i < n_reads; ++i)
+    if (!pile_invalid[i]) vlen.push_back(lengths[i]);
+  const u32 nv = static_cast<u32>(vlen.size());
+  std::vector<u32> batch_of(nv, 0);
+  u32 n_batches = 0;
+  {
+    u64 bytes = 0;
+    for (u32 i = 0; i < nv; ++i) {
+      batch_of[i] = n_batches;
+      bytes += vlen[i];
+      if (i != nv - 1 && bytes < batch_bases) continue;
+      bytes = 0;
+      ++n_batches;
+    }
+  }
+  std::vector<u64> work(nv);
+  for (u32 i = 0; i < nv; ++i) work[i] = vlen[i] * (n_batches - batch_of[i]);
+  const std::vector<u32> vb = partition_weights(work, g->world());
+  std::vector<const rvn::Pass2State*> loc(g->world(), nullptr);
+  std::vector<std::vector<u64>> per_batch(g->world());
+  Pass2Args A{packed, word_offsets, lengths, n_reads, pile_begin, pile_end, pile_invalid, freq, kmer_len, identity,
+              batch_bases, &vb, &loc, &per_batch, p.get()};
+  const int rc = run_ranks(g, [&](Rank& R) { pass2_rank(R, A); });
+  if (rc != RVN_OK) return rc;
+  *out = p.release();
+  return RVN_OK;
+}
+
+int rvn_group_filter_overlaps_by_identity(rvn_group* g, const uint64_t* packed, const uint64_t* word_offsets,
+                                          const uint32_t* lengths, uint32_t n_reads, rvn_overlap* overlaps, uint32_t* offsets,
+                                          const uint32_t* pile_begin, const uint32_t* pile_end, const uint8_t* pile_invalid,
+                                          double identity) {
+  if (!g || !offsets || (n_reads && (!packed || !word_offsets || !lengths || !pile_begin || !pile_end || !pile_invalid)) ||
+      (offsets[n_reads] && !overlaps)) {
+    rvn::set_last_error("[raven_hip] rvn_group_filter_overlaps_by_identity: NULL argument");
+    return RVN_EINVAL;
+  }
+  if (!reads_consistent(word_offsets, lengths, n_reads)) {
+    rvn::set_last_error("[raven_hip] rvn_group_filter_overlaps_by_identity: word_offsets inconsistent with lengths");
+    return RVN_EINVAL;
+  }
+  const u64 O = offsets[n_reads];
+  const rvn::Overlap* ovl = reinterpret_cast<const rvn::Overlap*>(overlaps);
+  for (u64 x = 0; x < O; ++x)
+    if (ovl[x].lhs_id >= n_reads || ovl[x].rhs_id >= n_reads) {
+      rvn::set_last_error("[raven_hip] rvn_group_filter_overlaps_by_identity: overlap of an unknown read");
+      return RVN_EINVAL;
+    }
+  for (u32 i = 0; i < n_reads; ++i)
+    if (offsets[i + 1] < offsets[i]) {
+      rvn::set_last_error("[raven_hip] rvn_group_filter_overlaps_by_identity: offsets not ascending");
+      return RVN_EINVAL;
+    }
+  if (O == 0) return RVN_OK;
+  // pile ranges balanced by the span lengths of their overlaps (the edit distance's work)
+  std::vector<u64> wgt(n_reads, 0);
+  for (u32 i = 0; i < n_reads; ++i)
+    for (u32 x = offsets[i]; x < offsets[i + 1]; ++x)
+      wgt[i] += static_cast<u64>(ovl[x].lhs_end - ovl[x].lhs_begin) + (ovl[x].rhs_end - ovl[x].rhs_begin) + 1;
+  const std::vector<u32> b = partition_weights(wgt, g->world());
+  std::vector<u8> ok(O, 0);
+  std::vector<rvn::Overlap> upd(O);
+  IdentityArgs A{packed, word_offsets, lengths, n_reads, ovl, offsets, pile_begin, pile_end, pile_invalid, identity, &b,
+                 ok.data(), upd.data()};
+  const int rc = run_ranks(g, [&](Rank& R) { identity_rank(R, A); });
+  if (rc != RVN_OK) return rc;
+  rvn::identity_filter_compact(reinterpret_cast<rvn::Overlap*>(overlaps), offsets, n_reads, ok.data(), upd.data());
+  return RVN_OK;
 }
 
 }  // extern "C"

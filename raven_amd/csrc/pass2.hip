@@ -262,24 +262,43 @@ void reads_subset(Engine& e, const ReadsDev& R, const std::vector<u32>& src, Rea
   reads_build_tiles(e, V);
 }
 
-// raven::FindOverlapsAndRepetetiveRegions (construct.cc:316-491); R = all reads with ids[i] == i
-void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid, double freq,
-                 u32 kmer_len, double identity, u64 batch_bases, Pass2State& out) {
+namespace {
+// dst[i] |= src[i] (the containment flags of several ranks' second passes)
+__global__ void or_bytes_kernel(u8* __restrict__ dst, const u8* __restrict__ src, u64 n) {
+  const u64 i = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] |= src[i];
+}
+}  // namespace
+
+void or_bytes(Engine& e, u8* d_dst, const u8* d_src, u64 n) {
+  if (n == 0) return;
+  or_bytes_kernel<<<div_up(n, 256), 256, 0, e.stream>>>(d_dst, d_src, n);
+  RVN_LAUNCH_CHECK();
+  RVN_HIP(rvn_stream_sync(e.stream));
+}
+
+// Stages of raven::FindOverlapsAndRepetetiveRegions (construct.cc:316-491) shared by the single engine (second_pass) and
+// the device group (group.hip): prepare (valid reads, k-mer cell offsets, index batches), one index batch with the
+// Map of a range of query reads, finish (de-duplication, invalidation, final OverlapUpdate sweep).
+// R = all reads with ids[i] == i.
+void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid,
+                         u64 batch_bases, Pass2State& out, Pass2Prep& P) {
   hipStream_t s = e.stream;
   const u32 n = R.n;
   out.n = n;
   out.n_overlaps = 0;
-  PileRegion* d_regions = upload_regions(e, h_begin, h_end, h_invalid, n);
+  P.batches.clear();
+  P.d_regions = upload_regions(e, h_begin, h_end, h_invalid, n);
   u8* d_contained = out.contained.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemsetAsync(d_contained, 0, static_cast<size_t>(n) + 16, s));
   // valid reads first, by id (construct.cc:324-349); index_of: id -> position among the valid reads
-  std::vector<u32> valid;
+  P.valid.clear();
   std::vector<u32> index_of(n, 0xFFFFFFFFu);
   out.h_kmers_off.assign(static_cast<size_t>(n) + 1, 0);
   for (u32 i = 0; i < n; ++i) {
     if (!h_invalid[i]) {
-      index_of[i] = static_cast<u32>(valid.size());
-      valid.push_back(i);
+      index_of[i] = static_cast<u32>(P.valid.size());
+      P.valid.push_back(i);
       out.h_kmers_off[i + 1] = out.h_kmers_off[i] + (static_cast<u64>(R.h_len[i]) >> kPSS2) + 1;
     } else {
       out.h_kmers_off[i + 1] = out.h_kmers_off[i];
@@ -288,74 +307,91 @@ void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_
   out.kmers_total = out.h_kmers_off[n];
   u8* d_kmers = out.kmers.get<u8>(out.kmers_total + 16);
   RVN_HIP(hipMemsetAsync(d_kmers, 0, out.kmers_total + 16, s));
+  const u32 nv = static_cast<u32>(P.valid.size());
+  P.h_v_kmers_off.assign(static_cast<size_t>(nv) + 1, out.kmers_total);
+  for (u32 i = 0; i < nv; ++i) P.h_v_kmers_off[i] = out.h_kmers_off[P.valid[i]];
   // construct.cc:343-349: `s` is the position of the FIRST INVALID pile after the valid-first sort and stays 0 when no
   // pile is invalid at all — the reference then maps nothing and overlaps.back() stays empty.  Reproduced on purpose
   // (results identical to the reference's on the same input); real read sets always have contained, hence invalid, piles.
-  const u32 sv = valid.size() == n ? 0u : static_cast<u32>(valid.size());
-  if (sv == 0) {
-    if (valid.size() == n && n > 0)  // (say so: an empty second pass otherwise looks like "no overlaps found")
+  P.sv = nv == n ? 0u : nv;
+  if (P.sv == 0) {
+    if (nv == n && n > 0)  // (say so: an empty second pass otherwise looks like "no overlaps found")
       std::fprintf(stderr, "[raven_hip] second pass: every pile is valid, so nothing is mapped — the reference's behaviour "
                            "(construct.cc:343-349), reproduced on purpose\n");
     RVN_HIP(rvn_stream_sync(s));
     return;
   }
-  ReadsDev V;
-  reads_subset(e, R, valid, V);
-  u32* d_index_of = e.p2_index_of.get<u32>(static_cast<size_t>(n) + 1);
-  RVN_HIP(hipMemcpyAsync(d_index_of, index_of.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
-  std::vector<u64> v_kmers_off(static_cast<size_t>(sv) + 1);
-  for (u32 i = 0; i < sv; ++i) v_kmers_off[i] = out.h_kmers_off[valid[i]];
-  v_kmers_off[sv] = out.kmers_total;
-  u64* d_v_kmers_off = e.p2_kmers_off.get<u64>(static_cast<size_t>(sv) + 1);
-  RVN_HIP(hipMemcpyAsync(d_v_kmers_off, v_kmers_off.data(), v_kmers_off.size() * 8, hipMemcpyHostToDevice, s));
+  const u32 sv = P.sv;
+  reads_subset(e, R, P.valid, P.V);
+  P.d_index_of = e.p2_index_of.get<u32>(static_cast<size_t>(n) + 1);
+  RVN_HIP(hipMemcpyAsync(P.d_index_of, index_of.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
+  P.d_v_kmers_off = e.p2_kmers_off.get<u64>(static_cast<size_t>(sv) + 1);
+  RVN_HIP(hipMemcpyAsync(P.d_v_kmers_off, P.h_v_kmers_off.data(), (static_cast<size_t>(sv) + 1) * 8, hipMemcpyHostToDevice, s));
   RVN_HIP(rvn_stream_sync(s));
-
-  u64 acc_n = 0;  // survivors of all batches so far, in the reference's merge order (out.ovl)
+  // index batches of batch_bases valid bases: [first, last) of the valid reads
   u64 bytes = 0;
   for (u32 i = 0, j = 0; i < sv; ++i) {
-    bytes += V.h_len[i];
+    bytes += P.V.h_len[i];
     if (i != sv - 1 && bytes < batch_bases) continue;
     bytes = 0;
-    engine_minimize(e, V, j, i + 1, false);
-    index_filter(e, freq);
-    MapOut& mo = e.map_out;
-    map_batch(e, V, 0, i + 1, true, true, false, true, mo);
-    e.c_intervals += mo.n_intervals;
-    // Pile::AddKmers(filtered, kmer_len, sequence) of every mapped read (construct.cc:382)
-    if (mo.n_query) {
-      RVN_KLAUNCH(kKAddKmers, add_kmers_flags_kernel<<<div_up(mo.n_query, 256), 256, 0, s>>>(
-                                  V.packed.as<u64>(), V.word_off.as<u64>(), mo.filtered.as<u8>(), e.query_sketch.org.as<u64>(),
-                                  e.query_sketch.read_off.as<u32>(), i + 1, mo.n_query, kmer_len, d_v_kmers_off, d_kmers));
-    }
-    const u64 O = mo.n_overlaps;
-    if (O) {
-      Overlap* d_ovl = mo.ovl.as<Overlap>();
-      u8* d_ok = e.p2_ok.get<u8>(O + 16);
-      u8* d_keep = e.p2_keep.get<u8>(O + 16);
-      update_and_identity(e, V, d_ovl, O, d_regions, d_index_of, identity, d_ok);
-      classify_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_ok, O, d_regions, d_contained, d_keep);
-      RVN_LAUNCH_CHECK();
-      u32* d_slot = e.p2_slot.get<u32>(O + 2);
-      exclusive_scan_u8_u32(d_keep, d_slot, O, e.scan_tmp, s);
-      const u64 m = read_back(e, d_slot + O, 4);
-      if (m) {
-        // append to the result list (grow-preserving)
-        if ((acc_n + m + 1) * sizeof(Overlap) > out.ovl.cap) {
-          DevBuf bigger;
-          bigger.reserve((acc_n + m + 1) * sizeof(Overlap) * 2);
-          if (acc_n) RVN_HIP(hipMemcpyAsync(bigger.ptr, out.ovl.ptr, acc_n * sizeof(Overlap), hipMemcpyDeviceToDevice, s));
-          RVN_HIP(rvn_stream_sync(s));
-          std::swap(out.ovl.ptr, bigger.ptr);
-          std::swap(out.ovl.cap, bigger.cap);
-        }
-        compact_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_keep, d_slot, O, out.ovl.as<Overlap>() + acc_n);
-        RVN_LAUNCH_CHECK();
-        acc_n += m;
-      }
-    }
+    P.batches.emplace_back(j, i + 1);
     j = i + 1;
   }
-  // consecutive overlaps of the same pair keep the longer one (construct.cc:444-453)
+}
+
+// Index batch [first, last) of the valid reads; the query reads [q_first, q_last) (inside [0, last)) are mapped against it
+// (the reference maps all of [0, last): construct.cc:362-383), their k-mer cells filled, their overlaps updated,
+// identity-filtered, classified and appended to out.ovl.  Returns the number appended.
+u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first, u32 q_last, double freq, u32 kmer_len,
+                      double identity, Pass2State& out) {
+  hipStream_t s = e.stream;
+  if (q_first >= q_last) return 0;
+  const ReadsDev& V = P.V;
+  engine_minimize(e, V, first, last, false);
+  index_filter(e, freq);
+  MapOut& mo = e.map_out;
+  map_batch(e, V, q_first, q_last, true, true, false, true, mo);
+  e.c_intervals += mo.n_intervals;
+  // Pile::AddKmers(filtered, kmer_len, sequence) of every mapped read (construct.cc:382)
+  if (mo.n_query) {
+    RVN_KLAUNCH(kKAddKmers, add_kmers_flags_kernel<<<div_up(mo.n_query, 256), 256, 0, s>>>(
+                                V.packed.as<u64>(), V.word_off.as<u64>() + q_first, mo.filtered.as<u8>(),
+                                e.query_sketch.org.as<u64>(), e.query_sketch.read_off.as<u32>(), q_last - q_first, mo.n_query,
+                                kmer_len, P.d_v_kmers_off + q_first, out.kmers.as<u8>()));
+  }
+  const u64 O = mo.n_overlaps;
+  if (O == 0) return 0;
+  const u64 acc_n = out.n_overlaps;
+  Overlap* d_ovl = mo.ovl.as<Overlap>();
+  u8* d_ok = e.p2_ok.get<u8>(O + 16);
+  u8* d_keep = e.p2_keep.get<u8>(O + 16);
+  update_and_identity(e, V, d_ovl, O, P.d_regions, P.d_index_of, identity, d_ok);
+  classify_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_ok, O, P.d_regions, out.contained.as<u8>(), d_keep);
+  RVN_LAUNCH_CHECK();
+  u32* d_slot = e.p2_slot.get<u32>(O + 2);
+  exclusive_scan_u8_u32(d_keep, d_slot, O, e.scan_tmp, s);
+  const u64 m = read_back(e, d_slot + O, 4);
+  if (m == 0) return 0;
+  // append to the result list (grow-preserving)
+  if ((acc_n + m + 1) * sizeof(Overlap) > out.ovl.cap) {
+    DevBuf bigger;
+    bigger.reserve((acc_n + m + 1) * sizeof(Overlap) * 2);
+    if (acc_n) RVN_HIP(hipMemcpyAsync(bigger.ptr, out.ovl.ptr, acc_n * sizeof(Overlap), hipMemcpyDeviceToDevice, s));
+    RVN_HIP(rvn_stream_sync(s));
+    std::swap(out.ovl.ptr, bigger.ptr);
+    std::swap(out.ovl.cap, bigger.cap);
+  }
+  compact_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_keep, d_slot, O, out.ovl.as<Overlap>() + acc_n);
+  RVN_LAUNCH_CHECK();
+  out.n_overlaps = acc_n + m;
+  return m;
+}
+
+// After the last batch, on the list in the reference's merge order: consecutive overlaps of the same pair keep the longer
+// one (construct.cc:444-453), contained piles become invalid (:466-470) in d_regions, the list is re-checked (:472-480).
+void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out) {
+  hipStream_t s = e.stream;
+  u64 acc_n = out.n_overlaps;
   if (acc_n) {
     u8* d_keep = e.p2_keep.get<u8>(acc_n + 16);
     RVN_HIP(hipMemsetAsync(d_keep, 1, acc_n, s));
@@ -363,9 +399,10 @@ void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_
     RVN_LAUNCH_CHECK();
     acc_n = compact(e, out.ovl, acc_n, d_keep, e.p2_slot, e.p2_tmp_ovl);
   }
-  // contained piles become invalid (construct.cc:466-470); the list is re-checked (construct.cc:472-480)
-  merge_invalid_kernel<<<div_up(n, 256), 256, 0, s>>>(d_regions, d_contained, n);
-  RVN_LAUNCH_CHECK();
+  if (out.n) {
+    merge_invalid_kernel<<<div_up(out.n, 256), 256, 0, s>>>(d_regions, out.contained.as<u8>(), out.n);
+    RVN_LAUNCH_CHECK();
+  }
   if (acc_n) {
     u8* d_ok = e.p2_ok.get<u8>(acc_n + 16);
     update_kernel<<<div_up(acc_n, 256), 256, 0, s>>>(out.ovl.as<Overlap>(), acc_n, d_regions, d_ok);
@@ -376,13 +413,22 @@ void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_
   out.n_overlaps = acc_n;
 }
 
-// The identity filter loop of ResolveContainedReads (construct.cc:162-217) on per-pile overlap lists (CSR, host, in
-// place): OverlapUpdate, edlib score of the two spans, survivors keep their updated coordinates and their order.
-void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_off, const u32* h_begin, const u32* h_end,
-                           const u8* h_invalid, double identity) {
+// raven::FindOverlapsAndRepetetiveRegions (construct.cc:316-491); R = all reads with ids[i] == i
+void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid, double freq,
+                 u32 kmer_len, double identity, u64 batch_bases, Pass2State& out) {
+  Pass2Prep P;
+  second_pass_prepare(e, R, h_begin, h_end, h_invalid, batch_bases, out, P);
+  if (P.sv == 0) return;
+  for (const auto& b : P.batches) second_pass_batch(e, P, b.first, b.second, 0, b.second, freq, kmer_len, identity, out);
+  second_pass_finish(e, P.d_regions, out);
+}
+
+// The identity filter loop of ResolveContainedReads (construct.cc:162-217) on a flat list of O overlaps (host):
+// OverlapUpdate + edlib score of the two spans; ok[x] = survives, upd[x] = the overlap with its updated coordinates.
+void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u64 O, const u32* h_begin, const u32* h_end,
+                           const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd) {
   hipStream_t s = e.stream;
   const u32 n = R.n;
-  const u64 O = h_off[n];
   if (O == 0) return;
   PileRegion* d_regions = upload_regions(e, h_begin, h_end, h_invalid, n);
   std::vector<u32> index_of(n);
@@ -393,14 +439,16 @@ void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_
   u8* d_ok = e.p2_ok.get<u8>(O + 16);
   RVN_HIP(hipMemcpyAsync(d_ovl, h_ovl, O * sizeof(Overlap), hipMemcpyHostToDevice, s));
   update_and_identity(e, R, d_ovl, O, d_regions, d_index_of, identity, d_ok);
-  std::vector<u8> ok(O);
-  std::vector<Overlap> upd(O);
-  RVN_HIP(hipMemcpyAsync(ok.data(), d_ok, O, hipMemcpyDeviceToHost, s));
-  RVN_HIP(hipMemcpyAsync(upd.data(), d_ovl, O * sizeof(Overlap), hipMemcpyDeviceToHost, s));
+  RVN_HIP(hipMemcpyAsync(h_ok, d_ok, O, hipMemcpyDeviceToHost, s));
+  RVN_HIP(hipMemcpyAsync(h_upd, d_ovl, O * sizeof(Overlap), hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
+}
+
+// per-pile compaction of the survivors (construct.cc:208-210): lists h_off[n + 1] of h_ovl, in place
+void identity_filter_compact(Overlap* h_ovl, u32* h_off, u32 n, const u8* ok, const Overlap* upd) {
   u64 k = 0;
   u32 prev_end = h_off[0];
-  for (u32 i = 0; i < n; ++i) {  // per-pile compaction of the survivors (construct.cc:208-210)
+  for (u32 i = 0; i < n; ++i) {
     const u32 b = prev_end, en = h_off[i + 1];
     prev_end = en;
     h_off[i] = static_cast<u32>(k);
@@ -408,6 +456,19 @@ void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_
       if (ok[x]) h_ovl[k++] = upd[x];
   }
   h_off[n] = static_cast<u32>(k);
+}
+
+// The identity filter loop of ResolveContainedReads (construct.cc:162-217) on per-pile overlap lists (CSR, host, in
+// place): OverlapUpdate, edlib score of the two spans, survivors keep their updated coordinates and their order.
+void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_off, const u32* h_begin, const u32* h_end,
+                           const u8* h_invalid, double identity) {
+  const u32 n = R.n;
+  const u64 O = h_off[n];
+  if (O == 0) return;
+  std::vector<u8> ok(O);
+  std::vector<Overlap> upd(O);
+  identity_filter_flags(e, R, h_ovl, O, h_begin, h_end, h_invalid, identity, ok.data(), upd.data());
+  identity_filter_compact(h_ovl, h_off, n, ok.data(), upd.data());
 }
 
 }  // namespace rvn

@@ -53,7 +53,7 @@ SYMBOLS = [
     "rvn_find_overlaps_and_repetitive_regions", "rvn_pass2_num_overlaps", "rvn_pass2_kmer_cells", "rvn_pass2_fetch",
     "rvn_pass2_destroy", "rvn_engine_release_scratch", "rvn_filter_overlaps_by_identity", "rvn_pass1_find_chimeric_regions",
     "rvn_reads_load", "rvn_reads_name", "rvn_reads_info", "rvn_reads_fetch", "rvn_engine_set_option", "rvn_overlap_update_and_type", "rvn_group_polish_round_q", "rvn_group_peer_access", "rvn_shard_sketch_range", "rvn_group_find_overlaps_and_create_piles_batched",
-    "rvn_polish_output_as_reads",
+    "rvn_polish_output_as_reads", "rvn_group_find_overlaps_and_repetitive_regions", "rvn_group_filter_overlaps_by_identity",
 ]
 
 # TEST INFRASTRUCTURE: what include/raven_hip_test.h declares on top (libraven_hip_test.so only)
@@ -162,6 +162,15 @@ def _declare(L):
     L.rvn_pass2_destroy.argtypes = [vp]
     L.rvn_engine_release_scratch.argtypes = [vp]
     L.rvn_filter_overlaps_by_identity.argtypes = [vp, vp, vp, vp, vp, vp, vp, dbl]
+    L.rvn_group_create.argtypes = [pp, u32, u32, u32, u32, u32, u32, vp, u32]
+    L.rvn_group_destroy.argtypes = [vp]
+    L.rvn_group_destroy.restype = None
+    L.rvn_group_size.argtypes = [vp]
+    L.rvn_group_size.restype = u32
+    L.rvn_group_engine.argtypes = [vp, u32]
+    L.rvn_group_engine.restype = vp
+    L.rvn_group_find_overlaps_and_repetitive_regions.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, dbl, u32, dbl, u64, pp]
+    L.rvn_group_filter_overlaps_by_identity.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, dbl]
     L.rvn_reads_load.argtypes = [vp, C.c_char_p, pp, vp]
     L.rvn_reads_name.argtypes = [vp, u32]
     L.rvn_reads_name.restype = C.c_char_p
@@ -978,6 +987,80 @@ class Engine:
 
     def set_timing(self, enabled: bool):
         lib().rvn_engine_set_timing(self._h, int(enabled))
+
+
+class Group:
+    """Several engines behind one handle (rvn_group_*): one per listed device, a device may repeat (virtual ranks).
+    The calls take host read sets (anything with packed / word_offsets / lengths, read i = id i) and return what the
+    single-engine calls of Engine return on the same input."""
+
+    def __init__(self, devices, k=15, w=5, bandwidth=500, chain=4, matches=100, gap=10000):
+        self.k, self.w = min(max(k, 1), 31), w
+        dev = np.ascontiguousarray(devices, dtype=np.int32)
+        h = C.c_void_p()
+        _check(lib().rvn_group_create(C.byref(h), k, w, bandwidth, chain, matches, gap, _p(dev), int(dev.shape[0])))
+        self._h = h
+
+    @property
+    def size(self):
+        return int(lib().rvn_group_size(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rvn_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def release_scratch(self):
+        """rvn_engine_release_scratch on every rank's engine."""
+        for r in range(self.size):
+            _check(lib().rvn_engine_release_scratch(lib().rvn_group_engine(self._h, r)))
+
+    @staticmethod
+    def _reads(rs):
+        return (np.ascontiguousarray(rs.packed, dtype=np.uint64), np.ascontiguousarray(rs.word_offsets, dtype=np.uint64),
+                np.ascontiguousarray(rs.lengths, dtype=np.uint32))
+
+    def find_overlaps_and_repetitive_regions(self, rs, pile_begin, pile_end, pile_invalid, freq=0.001, kmer_len=None,
+                                             identity=0.0, batch_bases=1 << 30):
+        """rvn_group_find_overlaps_and_repetitive_regions: the same dict as Engine.find_overlaps_and_repetitive_regions."""
+        n = int(rs.n)
+        pk, wo, ln = self._reads(rs)
+        b = np.ascontiguousarray(pile_begin, dtype=np.uint32)
+        en = np.ascontiguousarray(pile_end, dtype=np.uint32)
+        inv = np.ascontiguousarray(pile_invalid, dtype=np.uint8)
+        assert b.shape[0] == n and en.shape[0] == n and inv.shape[0] == n
+        h = C.c_void_p()
+        L = lib()
+        _check(L.rvn_group_find_overlaps_and_repetitive_regions(
+            self._h, _p(pk), _p(wo), _p(ln), n, _p(b), _p(en), _p(inv), float(freq),
+            int(self.k if kmer_len is None else kmer_len), float(identity), int(batch_bases), C.byref(h)))
+        try:
+            no, nk = int(L.rvn_pass2_num_overlaps(h)), int(L.rvn_pass2_kmer_cells(h))
+            ovl = np.zeros(no, dtype=OVERLAP_DTYPE)
+            contained = np.zeros(n, dtype=np.uint8)
+            kmers = np.zeros(nk, dtype=np.uint8)
+            koff = np.zeros(n + 1, dtype=np.uint64)
+            _check(L.rvn_pass2_fetch(h, _p(ovl), _p(contained), _p(kmers), _p(koff)))
+        finally:
+            L.rvn_pass2_destroy(h)
+        return dict(overlaps=ovl, contained=contained, kmers=[kmers[int(koff[i]):int(koff[i + 1])] for i in range(n)])
+
+    def filter_overlaps_by_identity(self, rs, overlaps, offsets, pile_begin, pile_end, pile_invalid, identity):
+        """rvn_group_filter_overlaps_by_identity: (overlaps, offsets) as Engine.filter_overlaps_by_identity returns them."""
+        pk, wo, ln = self._reads(rs)
+        o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE).copy()
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).copy()
+        _check(lib().rvn_group_filter_overlaps_by_identity(
+            self._h, _p(pk), _p(wo), _p(ln), int(rs.n), _p(o), _p(off), _p(np.ascontiguousarray(pile_begin, dtype=np.uint32)),
+            _p(np.ascontiguousarray(pile_end, dtype=np.uint32)), _p(np.ascontiguousarray(pile_invalid, dtype=np.uint8)),
+            float(identity)))
+        return o[:int(off[-1])], off
 
 
 def test_find_chimeric_regions(data):
