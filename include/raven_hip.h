@@ -184,6 +184,40 @@ uint64_t rvn_pass2_kmer_cells(const rvn_pass2* p);
 int rvn_pass2_fetch(const rvn_pass2* p, rvn_overlap* overlaps, uint8_t* contained, uint8_t* kmers, uint64_t* kmers_offsets);
 void rvn_pass2_destroy(rvn_pass2* p);
 
+/* raven::ResolveRepeatInducedOverlaps (RavenLib/src/construct.cc:493-559, called at :690), on the device: until an
+ * iteration removes nothing, ConnectedComponents (overlap_utils.cc:135-178: overlaps of GetOverlapType > 2 are edges,
+ * components that hold a valid pile), the nth_element median of each component's Pile::median(),
+ * Pile::FindRepetitiveRegions(median) of every member (pile.cc:230-317: k-mer groups, FindSlopes(1.42) pairs,
+ * MergeRegions, clip to the valid region), UpdateRepetitiveRegions of both piles of every overlap and the removal of the
+ * overlaps CheckRepetitiveRegions flags on either pile (pile.cc:319-369), survivors in order.
+ *   overlaps, n_overlaps   overlaps.back() as rvn_pass2_fetch gives it (coordinates in bases); not modified
+ *   coverage               Pile::data_ of every pile (uint16 per cell of 16 bases), pile i at coverage_offsets[i] ..
+ *                          coverage_offsets[i+1] (n_piles + 1 entries), as rvn_pass1_fetch_piles gives it after the
+ *                          host's ClearChimericRegions
+ *   kmers                  Pile::kmers_ (0/1 per cell; none: kmers_ empty), offsets as rvn_pass2_fetch gives them
+ *   pile_begin/end         Pile::begin() / Pile::end() in BASES (begin_ << 4), median = Pile::median(),
+ *                          invalid = Pile::is_invalid(); the piles hold no repetitive regions yet
+ * Result (rvn_repeats_fetch): the surviving overlaps (rvn_repeats_num_overlaps of them, in order), the piles'
+ * repetitive_regions_ after the last iteration as (first, second) uint32 pairs — first = cell << 1 | flag bit set by
+ * UpdateRepetitiveRegions, second = cell — pile i at region_offsets[i] .. region_offsets[i+1] (pairs; n_piles + 1
+ * entries; rvn_repeats_num_regions pairs in all), is_repetitive[n_piles] = set_is_repetitive() happened, and stats. */
+typedef struct rvn_repeats rvn_repeats;
+typedef struct rvn_repeats_stats {
+  uint32_t iterations; /* passes of the loop (the last one removes nothing) */
+  uint32_t components; /* components with a valid pile, in the first iteration */
+  uint64_t removed;    /* overlaps removed in all */
+} rvn_repeats_stats;
+int rvn_resolve_repeat_induced_overlaps(rvn_engine* e, const rvn_overlap* overlaps, uint64_t n_overlaps, uint32_t n_piles,
+                                        const uint16_t* coverage, const uint64_t* coverage_offsets, const uint8_t* kmers,
+                                        const uint64_t* kmers_offsets, const uint32_t* pile_begin, const uint32_t* pile_end,
+                                        const uint16_t* median, const uint8_t* invalid, rvn_repeats** out);
+uint64_t rvn_repeats_num_overlaps(const rvn_repeats* r);
+uint64_t rvn_repeats_num_regions(const rvn_repeats* r);
+/* every output may be NULL */
+int rvn_repeats_fetch(const rvn_repeats* r, rvn_overlap* overlaps, uint32_t* regions, uint32_t* region_offsets,
+                      uint8_t* is_repetitive, rvn_repeats_stats* stats);
+void rvn_repeats_destroy(rvn_repeats* r);
+
 /* The identity filter loop of raven::ResolveContainedReads (RavenLib/src/construct.cc:162-217) on the per-pile overlap
  * lists overlaps[i] (concatenated, offsets[n+1], both updated in place): every overlap goes through OverlapUpdate
  * (overlap_utils.cc:14-80; dropped when it fails), its two spans through the batched exact edit distance (rhs

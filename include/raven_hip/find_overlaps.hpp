@@ -14,6 +14,7 @@
 #ifndef RAVEN_HIP_FIND_OVERLAPS_HPP_
 #define RAVEN_HIP_FIND_OVERLAPS_HPP_
 
+#include <algorithm>
 #include <cstdint>
 #include <iostream>
 #include <memory>
@@ -160,6 +161,71 @@ void FindOverlapsAndRepetetiveRegions(const std::shared_ptr<thread_pool::ThreadP
   auto& back = overlaps.back();
   back.reserve(back.size() + flat.size());
   for (const auto& o : flat) back.emplace_back(ram::detail::ToOverlap(o));
+}
+
+// raven::ResolveRepeatInducedOverlaps (RavenLib/src/construct.cc:493-559, called at :690) with the reference's
+// signature: the loop of ConnectedComponents, FindRepetitiveRegions(component median), UpdateRepetitiveRegions and the
+// removal of the overlaps CheckRepetitiveRegions flags, on the device in one C-ABI call (an engine of its own on device
+// 0, as the reference's signature names none).  Rewrites overlaps.back() (survivors in order) and hands every pile its
+// final repetitive regions and is_repetitive flag.  `sequences` is not needed (ids equal positions, construct.cc:25).
+// PileT must provide begin(), end(), median(), is_invalid(), set_is_repetitive() (all raven::Pile members) and
+//   const std::vector<std::uint16_t>& coverage() const                         // Pile::data_
+//   std::size_t num_kmers() const; bool kmer(std::size_t i) const             // Pile::kmers_
+//   void AdoptRepetitiveRegions(const std::uint32_t* pairs, std::size_t n)    // replaces Pile::repetitive_regions_
+template <typename PileT>
+void ResolveRepeatInducedOverlaps(const std::shared_ptr<thread_pool::ThreadPool>& /*thread_pool*/,
+                                  const std::vector<std::unique_ptr<PileT>>& piles,
+                                  std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                                  const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& /*sequences*/) {
+  const std::size_t n = piles.size();
+  if (overlaps.empty()) overlaps.resize(1);
+  auto& back = overlaps.back();
+  std::vector<rvn_overlap> flat(back.size());
+  for (std::size_t i = 0; i < back.size(); ++i) {
+    const auto& o = back[i];
+    flat[i] = rvn_overlap{o.lhs_id, o.lhs_begin, o.lhs_end, o.rhs_id, o.rhs_begin, o.rhs_end, o.score, o.strand ? 1u : 0u};
+  }
+  std::vector<std::uint64_t> coff(n + 1, 0), koff(n + 1, 0);
+  for (std::size_t i = 0; i < n; ++i) {
+    coff[i + 1] = coff[i] + piles[i]->coverage().size();
+    koff[i + 1] = koff[i] + piles[i]->num_kmers();
+  }
+  std::vector<std::uint16_t> coverage(coff[n]);
+  std::vector<std::uint8_t> kmers(koff[n]), invalid(n);
+  std::vector<std::uint32_t> begin(n), end(n);
+  std::vector<std::uint16_t> median(n);
+  for (std::size_t i = 0; i < n; ++i) {
+    const auto& p = *piles[i];
+    std::copy(p.coverage().begin(), p.coverage().end(), coverage.begin() + coff[i]);
+    for (std::size_t k = 0; k < p.num_kmers(); ++k) kmers[koff[i] + k] = p.kmer(k) ? 1 : 0;
+    begin[i] = p.begin();
+    end[i] = p.end();
+    median[i] = p.median();
+    invalid[i] = p.is_invalid() ? 1 : 0;
+  }
+  struct Engine {
+    rvn_engine* e = nullptr;
+    ~Engine() { rvn_engine_destroy(e); }
+  } engine;
+  ram::detail::Check(rvn_engine_create(&engine.e, 15, 5, 500, 4, 100, 10000, 0));
+  rvn_repeats* r = nullptr;
+  ram::detail::Check(rvn_resolve_repeat_induced_overlaps(engine.e, flat.data(), flat.size(), static_cast<std::uint32_t>(n),
+                                                         coverage.data(), coff.data(), kmers.data(), koff.data(),
+                                                         begin.data(), end.data(), median.data(), invalid.data(), &r));
+  struct Guard {
+    rvn_repeats* r;
+    ~Guard() { rvn_repeats_destroy(r); }
+  } guard{r};
+  flat.resize(rvn_repeats_num_overlaps(r));
+  std::vector<std::uint32_t> regions(2 * rvn_repeats_num_regions(r)), roff(n + 1);
+  std::vector<std::uint8_t> is_repetitive(n);
+  ram::detail::Check(rvn_repeats_fetch(r, flat.data(), regions.data(), roff.data(), is_repetitive.data(), nullptr));
+  back.clear();
+  for (const auto& o : flat) back.emplace_back(ram::detail::ToOverlap(o));
+  for (std::size_t i = 0; i < n; ++i) {
+    piles[i]->AdoptRepetitiveRegions(regions.data() + 2 * static_cast<std::size_t>(roff[i]), roff[i + 1] - roff[i]);
+    if (is_repetitive[i]) piles[i]->set_is_repetitive();
+  }
 }
 
 }  // namespace raven

@@ -3,8 +3,10 @@
 
 #include <string>
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -426,6 +428,23 @@ void pile_add_kmers_batch(Engine& e, const ReadsDev& r, const u32* h_pos, const 
                           u32 first_read, u8* h_out, const u64* h_out_off);
 // Pile::AddLayers on a single pile (ps initialised for one read); h_ovl is a host array
 void pile_add_layers_single(Engine& e, PileState& ps, const u32* d_ids, const Overlap* h_ovl, u32 n);
+
+// raven::ResolveRepeatInducedOverlaps (repeats.hip): the surviving overlaps in order, the last iteration's regions of
+// every pile ((first, second) pairs, flag in bit 0 of first; CSR roff[n + 1]), is_repetitive, and the loop's counts
+struct RepeatResult {
+  std::vector<Overlap> ovl;
+  std::vector<u32> roff, reg;
+  std::vector<u8> isrep;
+  u32 iterations = 0, components = 0;
+  u64 removed = 0;
+};
+// a stage entry point's body under the engine's lock and error handling (engine.hip guarded(): HIP errors, host memory,
+// invalid arguments, and one rerun from released scratch when the device runs out of memory)
+int engine_guarded(Engine* e, const std::function<int()>& f);
+void set_last_error(const std::string& msg);
+void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32 n, const u16* h_cov, const u64* h_cov_off,
+                                     const u8* h_kmers, const u64* h_kmer_off, const u32* h_begin, const u32* h_end,
+                                     const u16* h_median, const u8* h_invalid, RepeatResult& res);
 
 }  // namespace rvn
 

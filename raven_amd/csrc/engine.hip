@@ -3,6 +3,7 @@
 
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -110,6 +111,14 @@ int guarded(Engine* e, F f) {
   }
   return guarded(f);
 }
+
+}  // namespace
+
+namespace rvn {
+int engine_guarded(Engine* e, const std::function<int()>& f) { return guarded(e, f); }
+}  // namespace rvn
+
+namespace {
 
 const char* kStageNames[StageTimes::kNum] = {"sketch", "sort", "index", "filter", "query_sketch", "match",
                                              "seg_sort", "intervals", "chain", "compact", "merge", "pile",

@@ -54,6 +54,8 @@ SYMBOLS = [
     "rvn_pass2_destroy", "rvn_engine_release_scratch", "rvn_filter_overlaps_by_identity", "rvn_pass1_find_chimeric_regions",
     "rvn_reads_load", "rvn_reads_name", "rvn_reads_info", "rvn_reads_fetch", "rvn_engine_set_option", "rvn_overlap_update_and_type", "rvn_group_polish_round_q", "rvn_group_peer_access", "rvn_shard_sketch_range", "rvn_group_find_overlaps_and_create_piles_batched",
     "rvn_polish_output_as_reads", "rvn_group_find_overlaps_and_repetitive_regions", "rvn_group_filter_overlaps_by_identity",
+    "rvn_resolve_repeat_induced_overlaps", "rvn_repeats_num_overlaps", "rvn_repeats_num_regions", "rvn_repeats_fetch",
+    "rvn_repeats_destroy",
 ]
 
 # TEST INFRASTRUCTURE: what include/raven_hip_test.h declares on top (libraven_hip_test.so only)
@@ -808,6 +810,47 @@ class Engine:
         finally:
             L.rvn_pass2_destroy(h)
         return dict(overlaps=ovl, contained=contained, kmers=[kmers[int(koff[i]):int(koff[i + 1])] for i in range(n)])
+
+    def resolve_repeat_induced_overlaps(self, overlaps, coverage, coverage_offsets, kmers, kmers_offsets, pile_begin,
+                                        pile_end, median, invalid):
+        """raven::ResolveRepeatInducedOverlaps on the device (rvn_resolve_repeat_induced_overlaps): overlaps.back(), the
+        piles' coverage / k-mer cells as flat arrays + offsets[n + 1], begin / end in bases, median, invalid 0/1.
+        Returns dict(overlaps (survivors, in order), regions ((k, 2) uint32: cell << 1 | flag, cell), region_offsets[n + 1]
+        (pairs), is_repetitive[n], iterations, components, removed)."""
+        o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)
+        cov = np.ascontiguousarray(coverage, dtype=np.uint16)
+        coff = np.ascontiguousarray(coverage_offsets, dtype=np.uint64)
+        km = np.ascontiguousarray(kmers, dtype=np.uint8)
+        koff = np.ascontiguousarray(kmers_offsets, dtype=np.uint64)
+        b = np.ascontiguousarray(pile_begin, dtype=np.uint32)
+        en = np.ascontiguousarray(pile_end, dtype=np.uint32)
+        med = np.ascontiguousarray(median, dtype=np.uint16)
+        inv = np.ascontiguousarray(invalid, dtype=np.uint8)
+        n = b.shape[0]
+        assert en.shape[0] == n and med.shape[0] == n and inv.shape[0] == n and coff.shape[0] == n + 1 == koff.shape[0]
+        h = C.c_void_p()
+        L = lib()
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.rvn_resolve_repeat_induced_overlaps.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
+        L.rvn_repeats_num_overlaps.argtypes = [vp]
+        L.rvn_repeats_num_overlaps.restype = u64
+        L.rvn_repeats_num_regions.argtypes = [vp]
+        L.rvn_repeats_num_regions.restype = u64
+        L.rvn_repeats_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.rvn_repeats_destroy.argtypes = [vp]
+        _check(L.rvn_resolve_repeat_induced_overlaps(self._h, _p(o), o.shape[0], n, _p(cov), _p(coff), _p(km), _p(koff),
+                                                     _p(b), _p(en), _p(med), _p(inv), C.byref(h)))
+        try:
+            ovl = np.zeros(int(L.rvn_repeats_num_overlaps(h)), dtype=OVERLAP_DTYPE)
+            reg = np.zeros((int(L.rvn_repeats_num_regions(h)), 2), dtype=np.uint32)
+            roff = np.zeros(n + 1, dtype=np.uint32)
+            isrep = np.zeros(n, dtype=np.uint8)
+            stats = np.zeros(2, dtype=np.uint64)  # rvn_repeats_stats: {u32 iterations, u32 components}, u64 removed
+            _check(L.rvn_repeats_fetch(h, _p(ovl), _p(reg), _p(roff), _p(isrep), _p(stats)))
+        finally:
+            L.rvn_repeats_destroy(h)
+        return dict(overlaps=ovl, regions=reg, region_offsets=roff, is_repetitive=isrep,
+                    iterations=int(stats[0]) & 0xFFFFFFFF, components=int(stats[0]) >> 32, removed=int(stats[1]))
 
     def filter_overlaps_by_identity(self, reads: Reads, overlaps, offsets, pile_begin, pile_end, pile_invalid, identity):
         """Identity filter loop of ResolveContainedReads on per-pile lists: returns (overlaps, offsets) filtered."""
