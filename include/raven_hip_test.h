@@ -72,6 +72,18 @@ int rvn_test_inflate_fast(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t
  * block allocated by operation -ops[i] (out[i] = 1, or 0 if it was not in use); state[3] = {bytes free, largest hole,
  * blocks in use} afterwards. */
 int rvn_test_freelist(uint64_t size, uint64_t grain, const int64_t* ops, uint32_t n_ops, int64_t* out, uint64_t* state);
+/* The lane-per-pair edit-distance kernel (edit_distance.hip: ed_lane_kernel<W>) stepped on the CPU: its per-pair body is
+ * one __host__ __device__ function without a cross-lane operation, called here pair by pair.  packed / word_off: a packed
+ * read set as rvn_reads_upload takes it (one pad word behind the last read); pairs: n x {a_idx, a_begin, a_len, b_idx,
+ * b_begin, b_len, strand, 0}, strand 0 = the b span is reverse-complemented; kmax (nullable): per-pair threshold of the
+ * bounded mode; W = 3, 5 or 7 slots of the window.  out[p] = the RAW value the kernel stores: the exact distance when it
+ * is <= min(threshold of the window, kmax), else one of
+ *   0xFFFFFFFE  the distance is above the pair's kmax (bounded mode; its value is not needed),
+ *   0xFFFFFFFF  beyond the window of W = 3 or 5 slots (the widest window may still decide the pair),
+ *   0xFFFFFFFD  beyond the widest window, W = 7 (the pair goes to the wave-per-pair kernel).
+ * Returns 0, RVN_EINVAL for a NULL argument or another W. */
+int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off, const uint32_t* pairs, uint32_t n,
+                     const uint32_t* kmax, int W, uint32_t* out);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

@@ -22,6 +22,9 @@
 #include "engine.h"
 #include "myers.h"
 #include "wave.h"
+#ifdef RVN_TEST_HOOKS
+#include "../../include/raven_hip_test.h"
+#endif
 
 namespace rvn {
 
@@ -188,7 +191,7 @@ struct TextGroups {
   u32 m;
   bool rc;
   u64 cur, nxt;     // bases of columns 32 g + 1 .. 32 g + 32 (2 bits each, column order) of the current / next group
-  __device__ __forceinline__ u64 fetch(long long j0) const {  // columns j0 .. j0 + 31
+  __host__ __device__ __forceinline__ u64 fetch(long long j0) const {  // columns j0 .. j0 + 31
     if (j0 > static_cast<long long>(m)) return 0;
     const long long span_last32 = m >= 32 ? lo + m - 32 : lo;  // last start whose 32 bases stay inside the span
     if (!rc) {
@@ -199,11 +202,11 @@ struct TextGroups {
     const long long top = first - (j0 - 1);  // base of column j0; the columns go DOWN from it
     long long s = top - 31;
     if (s < lo) s = lo;
-    u64 y = __brevll(load_bases32(words, static_cast<u64>(s)));  // pair at offset o -> pair 31 - o, its two bits swapped
+    u64 y = RVN_BREV64(load_bases32(words, static_cast<u64>(s)));  // pair at offset o -> pair 31 - o, its two bits swapped
     y = ((y & 0x5555555555555555ULL) << 1) | ((y >> 1) & 0x5555555555555555ULL);
     return ~(y >> (2 * (31 - (top - s))));  // column j0 + t = offset (top - s) - t -> pair t; complement = 3 - code
   }
-  __device__ __forceinline__ void init(const u64* w, u64 b_base, u32 m_, bool rc_) {
+  __host__ __device__ __forceinline__ void init(const u64* w, u64 b_base, u32 m_, bool rc_) {
     words = w;
     rc = rc_;
     m = m_;
@@ -213,7 +216,7 @@ struct TextGroups {
     nxt = fetch(33);
   }
   // call once per column, in column order
-  __device__ __forceinline__ unsigned get(int j) {
+  __host__ __device__ __forceinline__ unsigned get(int j) {
     const int x = (j - 1) & 31;
     if (x == 0 && j > 1) {  // (wave-uniform)
       cur = nxt;
@@ -228,7 +231,7 @@ struct PeqRaw {
   u64 w[4];
   u32 row0;
 };
-__device__ __forceinline__ void peq_raw_load(const u64* __restrict__ words, u64 a_base, u32 n, u32 b, PeqRaw& r) {
+__host__ __device__ __forceinline__ void peq_raw_load(const u64* __restrict__ words, u64 a_base, u32 n, u32 b, PeqRaw& r) {
   r.row0 = b * 64;
   r.w[0] = r.w[1] = r.w[2] = r.w[3] = 0;
   if (r.row0 < n) {  // exactly the words load_peq touches
@@ -239,7 +242,7 @@ __device__ __forceinline__ void peq_raw_load(const u64* __restrict__ words, u64 
     if (off && second) r.w[2] = words[(bit >> 6) + 2];
   }
 }
-__device__ __forceinline__ void peq_from_raw(const PeqRaw& r, u64 a_base, u32 n, u64 (&peq)[4]) {
+__host__ __device__ __forceinline__ void peq_from_raw(const PeqRaw& r, u64 a_base, u32 n, u64 (&peq)[4]) {
   const unsigned off = static_cast<unsigned>(((a_base + r.row0) * 2) & 63);
   u64 lo = r.w[0] >> off, hi = r.w[1] >> off;
   if (off) {
@@ -279,7 +282,7 @@ __device__ __forceinline__ void peq_from_raw(const PeqRaw& r, u64 a_base, u32 n,
 // predicates of the slot loop: the band, and with it every result and every overflow decision, is the one of rounds 1-5
 // for the same threshold.
 template <int W>
-__device__ __forceinline__ u32 ed_lane_threshold(u32 n, u32 m, u32 km, bool* fits) {
+__host__ __device__ __forceinline__ u32 ed_lane_threshold(u32 n, u32 m, u32 km, bool* fits) {
   const u32 d = n > m ? n - m : m - n;
   // lo = s + (m > n ? d : 0), hi = s + (n > m ? d : 0); the largest s with ceil(lo / 64) + ceil(hi / 64) <= W - 1:
   // a units for the side without d, the rest for the side with it
@@ -295,34 +298,26 @@ __device__ __forceinline__ u32 ed_lane_threshold(u32 n, u32 m, u32 km, bool* fit
   return k > km ? km : k;
 }
 
+// The per-pair body of ed_lane_kernel<W>: the value the kernel stores to out[p] (km = the pair's threshold, 0xFFFFFFF0 if
+// none).  No cross-lane operation, so the test library steps the same code on the host (rvn_test_ed_lane).
 template <int W>
-__global__ __launch_bounds__(64) void ed_lane_kernel(const u64* __restrict__ packed, const u64* __restrict__ word_off,
-                                                    const EdPair* __restrict__ pairs, const u32* __restrict__ order,
-                                                    u32 n_order, const u32* __restrict__ kmax, u32* __restrict__ out) {
-  const u32 q = blockIdx.x * 64 + threadIdx.x;
-  if (q >= n_order) return;
-  const u32 p = order[q];
-  const EdPair pr = pairs[p];
+__host__ __device__ __forceinline__ u32 ed_lane_pair(const u64* __restrict__ packed, const u64* __restrict__ word_off,
+                                                     const EdPair& pr, u32 km) {
   const u32 n = pr.a_len, m = pr.b_len;
-  const u32 km = kmax ? kmax[p] : 0xFFFFFFF0u;
-  if (n == 0 || m == 0) {
-    out[p] = (n + m) > km ? kEdAbove : n + m;
-    return;
-  }
+  if (n == 0 || m == 0) return (n + m) > km ? kEdAbove : n + m;
   const u32 d = n > m ? n - m : m - n;
-  if (d > km) {
-    out[p] = kEdAbove;
-    return;
-  }
+  if (d > km) return kEdAbove;
   constexpr u32 kOverflow = W >= kEdLaneWidest ? kEdOverflowWide : kEdOverflow;
   bool fits;
   const u32 k = ed_lane_threshold<W>(n, m, km, &fits);
-  if (!fits) {
-    out[p] = kOverflow;
-    return;
-  }
-  const int lo = static_cast<int>((k - d) / 2 + (m > n ? d : 0u));  // band rows above the diagonal: block t is in the band
-  const int hi = static_cast<int>((k - d) / 2 + (n > m ? d : 0u));  // of column j while 64 t - hi + 1 <= j <= 64 t + 64 + lo
+  if (!fits) return kOverflow;
+  // A block takes its entry bound from the block above at the column before: the band must be at least one row wide
+  // beside the diagonal (lo + hi >= 1), or that block has left when this one comes in.  Spans of equal length with a
+  // threshold of 0 or 1 (kmax of a short overlap) get the band of threshold 2: what is <= k is still exact, what is not
+  // is still above k.
+  const u32 half = (d == 0 && k < 2) ? 1u : (k - d) / 2;
+  const int lo = static_cast<int>(half + (m > n ? d : 0u));  // band rows above the diagonal: block t is in the band
+  const int hi = static_cast<int>(half + (n > m ? d : 0u));  // of column j while 64 t - hi + 1 <= j <= 64 t + 64 + lo
   const int nb = static_cast<int>((n + 63) >> 6);
   const int sL = (lo + 63) >> 6;  // the window's first block in cycle c (columns 64 c + 1 .. 64 c + 64): max(0, c - sL)
   const u64* aw = packed + word_off[pr.a_idx];
@@ -401,11 +396,19 @@ __global__ __launch_bounds__(64) void ed_lane_kernel(const u64* __restrict__ pac
       }
     }
   }
-  u32 res;
-  if (result <= k) res = result;
-  else if (k >= km) res = kEdAbove;
-  else res = kOverflow;
-  out[p] = res;
+  if (result <= k) return result;
+  return k >= km ? kEdAbove : kOverflow;
+}
+
+template <int W>
+__global__ __launch_bounds__(64) void ed_lane_kernel(const u64* __restrict__ packed, const u64* __restrict__ word_off,
+                                                    const EdPair* __restrict__ pairs, const u32* __restrict__ order,
+                                                    u32 n_order, const u32* __restrict__ kmax, u32* __restrict__ out) {
+  const u32 q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= n_order) return;
+  const u32 p = order[q];
+  const EdPair pr = pairs[p];
+  out[p] = ed_lane_pair<W>(packed, word_off, pr, kmax ? kmax[p] : 0xFFFFFFF0u);
 }
 
 __global__ void ed_keys_kernel(const EdPair* __restrict__ pairs, u32 n, u32* __restrict__ keys, u32* __restrict__ vals) {
@@ -528,7 +531,29 @@ __global__ __launch_bounds__(64) void ed_full_kernel(const u64* __restrict__ pac
   if (lane == 0) out[p] = result - 1u;
 }
 
+#ifdef RVN_TEST_HOOKS
+template <int W>
+void ed_lane_host(const u64* packed, const u64* word_off, const EdPair* pairs, u32 n, const u32* kmax, u32* out) {
+  for (u32 p = 0; p < n; ++p) out[p] = ed_lane_pair<W>(packed, word_off, pairs[p], kmax ? kmax[p] : 0xFFFFFFF0u);
+}
+#endif
+
 }  // namespace
+
+#ifdef RVN_TEST_HOOKS
+extern "C" int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off, const uint32_t* pairs, uint32_t n,
+                                const uint32_t* kmax, int W, uint32_t* out) {
+  if (!packed || !word_off || (n && (!pairs || !out))) return RVN_EINVAL;
+  const EdPair* pr = reinterpret_cast<const EdPair*>(pairs);
+  switch (W) {
+    case 3: ed_lane_host<3>(packed, word_off, pr, n, kmax, out); break;
+    case 5: ed_lane_host<5>(packed, word_off, pr, n, kmax, out); break;
+    case kEdLaneWidest: ed_lane_host<kEdLaneWidest>(packed, word_off, pr, n, kmax, out); break;
+    default: return RVN_EINVAL;
+  }
+  return RVN_OK;
+}
+#endif  // RVN_TEST_HOOKS
 
 // pairs and results resident in HBM: d_pairs = n_pairs x {a_idx,a_begin,a_len,b_idx,b_begin,b_len,strand,0}, d_out u32[n].
 // d_kmax (nullable): per-pair thresholds — distances above them come back as 0xFFFFFFFE (see ed_banded_kernel).

@@ -10,8 +10,10 @@ namespace rvn {
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RVN_POPC64(x) __popcll(x)
+#define RVN_BREV64(x) __brevll(x)
 #else
 #define RVN_POPC64(x) __builtin_popcountll(x)
+#define RVN_BREV64(x) __builtin_bitreverse64(x)
 #endif
 
 // edlib calculateBlock: advance one 64-row block by one column. hin/hout in {-1, 0, +1}.

@@ -62,7 +62,7 @@ SYMBOLS = [
 TEST_SYMBOLS = [
     "rvn_poa_banded_emulate", "rvn_test_low_complexity", "rvn_test_nw_breakpoints", "rvn_test_hash",
     "rvn_test_canonical", "rvn_test_std_sort_lendesc", "rvn_test_heap_sort_lendesc", "rvn_test_overlap_update_and_type", "rvn_test_find_chimeric_regions",
-    "rvn_test_parse_file", "rvn_test_freelist", "rvn_test_inflate_fast",
+    "rvn_test_parse_file", "rvn_test_freelist", "rvn_test_inflate_fast", "rvn_test_ed_lane",
 ]
 
 
@@ -120,6 +120,8 @@ def test_lib():
     L.rvn_test_parse_file.argtypes = [C.c_char_p, i32, u32, i32, u64, pp, pp, pp, C.POINTER(u32), pp, vp]
     L.rvn_test_freelist.argtypes = [u64, u64, vp, u32, vp, vp]
     L.rvn_test_inflate_fast.argtypes = [vp, u64, vp, u64, u64, vp]
+    L.rvn_test_ed_lane.argtypes = [vp, vp, vp, u32, vp, i32, vp]
+    L.rvn_test_ed_lane.restype = i32
     _test_lib = L
     return L
 
@@ -1167,6 +1169,26 @@ def test_parse_file(path, fastq, threads=0, force_streaming=False, slab_bytes=0)
     qs = [quals[off[i]:off[i + 1]] for i in range(n.value)] if fastq else None
     return names, seqs, qs, dict(gzip=int(info[0]), streaming=int(info[1]), members=int(info[2]), threads=int(info[3]),
                                  restarted=int(info[4]), loop_s=info[5] / 1e6, scan_s=info[6] / 1e6, fast=int(info[7]))
+
+
+ED_ABOVE, ED_OVERFLOW, ED_OVERFLOW_WIDE = 0xFFFFFFFE, 0xFFFFFFFF, 0xFFFFFFFD  # raw codes of the lane kernel
+
+
+def test_ed_lane(packed, word_offsets, pairs, W, kmax=None):
+    """TEST INFRASTRUCTURE: the per-pair body of ed_lane_kernel<W> (edit_distance.hip) on the host, no GPU needed.  pairs:
+    ED_PAIR_DTYPE; kmax: uint32 per pair or None; returns the raw uint32 the kernel stores per pair: the exact distance,
+    ED_ABOVE (above kmax), ED_OVERFLOW (beyond a window of 3 / 5 slots) or ED_OVERFLOW_WIDE (beyond the widest, 7)."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint64)
+    wo = np.ascontiguousarray(word_offsets, dtype=np.uint64)
+    pairs = np.ascontiguousarray(pairs, dtype=ED_PAIR_DTYPE)
+    km = None if kmax is None else np.ascontiguousarray(kmax, dtype=np.uint32)
+    assert km is None or km.shape[0] == pairs.shape[0]
+    out = np.zeros(pairs.shape[0], dtype=np.uint32)
+    rc = test_lib().rvn_test_ed_lane(_p(packed), _p(wo), _p(pairs), pairs.shape[0], None if km is None else _p(km), int(W),
+                                     _p(out))
+    if rc != 0:
+        raise ValueError("rvn_test_ed_lane: %d" % rc)
+    return out
 
 
 NW_REC_DTYPE = np.dtype([("first_t", "<u4"), ("first_q", "<u4"), ("last_t", "<u4"), ("last_q", "<u4"),
