@@ -148,7 +148,7 @@ int rvn_pass1_fetch_piles(const rvn_pass1* p, uint16_t* data, uint64_t* offsets)
  * (pile.cc:122-174) for every pile.  begin / end in cells (Pile::begin_ / end_, i.e. bases >> 4), invalid = the
  * pile's is_invalid flag (the caller clears overlaps[i] for those, construct.cc:134-135); the coverage of valid piles
  * is zeroed outside the region exactly as UpdateValidRegion does (visible through rvn_pass1_fetch_piles).
- * FindChimericRegions (double-precision slopes) stays on the host. */
+ * The result also stays with the pass, for rvn_pass1_resolve.  FindChimericRegions: rvn_pass1_find_chimeric_regions. */
 int rvn_pass1_trim_and_annotate(rvn_pass1* p, uint32_t coverage, uint32_t* begin, uint32_t* end, uint16_t* median,
                                 uint8_t* invalid);
 /* The third step of raven::TrimAndAnnotatePiles (construct.cc:139): Pile::FindChimericRegions (pile.cc:176-187) =
@@ -217,6 +217,61 @@ uint64_t rvn_repeats_num_regions(const rvn_repeats* r);
 int rvn_repeats_fetch(const rvn_repeats* r, rvn_overlap* overlaps, uint32_t* regions, uint32_t* region_offsets,
                       uint8_t* is_repetitive, rvn_repeats_stats* stats);
 void rvn_repeats_destroy(rvn_repeats* r);
+
+/* The tail of stage -5 of raven::ConstructGraph on the device, in two phases (`phases`: bit 0 | bit 1):
+ *   1  raven::ResolveContainedReads (RavenLib/src/construct.cc:154-248): the identity filter loop when identity != 0
+ *      (:162-217), then for every overlap in list order OverlapUpdate and GetOverlapType (:221-237) — type 1 with an rhs
+ *      pile that is not is_maybe_chimeric() marks pile i contained, type 2 with pile i not is_maybe_chimeric() marks the
+ *      rhs pile, both drop the overlap, everything else is kept with its updated coordinates — and every contained pile
+ *      made invalid with its list emptied (:238-244);
+ *   2  raven::ResolveChimericSequences (construct.cc:250-314): the nth_element median of the non-zero Pile::median() of
+ *      all piles (:259-267), Pile::ClearChimericRegions(median) with UpdateValidRegion on every pile that is not invalid
+ *      (:270-282; pile.cc:189-228, :144-157), OverlapUpdate of every remaining overlap and the containment marks of
+ *      types 1 and 2 (:287-308), the lists cleared (:310).  When no pile has a non-zero median the reference reads an
+ *      empty vector; a valid pile always has one, so there is no valid pile either and the state is returned unchanged
+ *      (lists included).
+ * A result (rvn_resolved_fetch, every output may be NULL): begin / end (cells, Pile::begin_ / end_), invalid, contained,
+ * chimeric (set_is_chimeric() happened) per pile; the piles' remaining chimeric_regions_ as (first, second) cell pairs,
+ * pile i at region_offsets[i] .. region_offsets[i+1] (pairs; n + 1 entries; rvn_resolved_num_regions pairs in all);
+ * the global median of phase 2 (0: it did not run or changed nothing); the lists (rvn_resolved_num_overlaps entries)
+ * and offsets[n + 1] as they stand after the last phase that ran (empty after phase 2); the coverage of the host-array
+ * form (rvn_resolved_coverage_words cells; the resident form leaves it on the pass); stats. */
+typedef struct rvn_resolved rvn_resolved;
+typedef struct rvn_resolve_stats {
+  uint64_t dropped_by_update[2];   /* overlaps OverlapUpdate dropped in the marking loop of phase 1 / in phase 2 */
+  uint64_t dropped_by_filter;      /* overlaps the identity filter loop dropped (OverlapUpdate or the score) */
+  uint64_t dropped_by_containment; /* type 1 / 2 overlaps of phase 1 that marked a pile */
+  uint32_t contained[2];           /* piles that became contained in phase 1 / phase 2 */
+  uint32_t cut;                    /* piles whose valid region ClearChimericRegions changed (set_is_chimeric) */
+  uint32_t invalidated;            /* piles UpdateValidRegion made invalid in ClearChimericRegions */
+} rvn_resolve_stats;
+/* ... on a first pass whose lists and coverage are in HBM (replaces construct.cc:671-674 for a caller that keeps its
+ * piles on the device).  Runs raven::TrimAndAnnotatePiles (construct.cc:123-152, FindValidRegion(coverage)) first when
+ * the pass has not been trimmed yet, and FindChimericRegions with its result left in HBM.  A phase runs once per pass:
+ * phases = 1 and later phases = 2 give what phases = 3 gives.  The lists of a result of phase 1 are read from the pass:
+ * fetch them before phase 2 runs on it.  r: the reads of the pass, needed when identity != 0 (else it may be NULL).
+ * Afterwards the coverage of the pass (rvn_pass1_fetch_piles) is what the reference's piles hold; the lists
+ * rvn_pass1_fetch_overlaps gives are still the first pass's. */
+int rvn_pass1_resolve(rvn_pass1* p, const rvn_reads* r, uint32_t coverage, double identity, uint32_t phases,
+                      rvn_resolved** out);
+/* ... on the caller's arrays (replaces construct.cc:154-248 and :250-314 behind their signatures): overlaps / offsets
+ * as rvn_pass1_fetch_overlaps gives them (every entry of list i has lhs_id == i, construct.cc:74-75), coverage /
+ * coverage_offsets as rvn_pass1_fetch_piles, regions / region_offsets as rvn_pass1_find_chimeric_regions, begin / end
+ * (cells) / median / invalid as rvn_pass1_trim_and_annotate.  Nothing is modified.  RVN_EINVAL when an entry of list i
+ * has another lhs_id, an id is out of range, or a region or valid region leaves its pile. */
+int rvn_resolve_contained_and_chimeric(rvn_engine* e, const rvn_reads* r, const rvn_overlap* overlaps,
+                                       const uint32_t* offsets, uint32_t n_piles, const uint16_t* coverage,
+                                       const uint64_t* coverage_offsets, const uint32_t* regions,
+                                       const uint32_t* region_offsets, const uint32_t* begin, const uint32_t* end,
+                                       const uint16_t* median, const uint8_t* invalid, double identity, uint32_t phases,
+                                       rvn_resolved** out);
+uint64_t rvn_resolved_num_overlaps(const rvn_resolved* r);
+uint64_t rvn_resolved_num_regions(const rvn_resolved* r);
+uint64_t rvn_resolved_coverage_words(const rvn_resolved* r);
+int rvn_resolved_fetch(const rvn_resolved* r, uint32_t* begin, uint32_t* end, uint8_t* invalid, uint8_t* contained,
+                       uint8_t* chimeric, uint32_t* regions, uint32_t* region_offsets, uint16_t* median,
+                       rvn_overlap* overlaps, uint32_t* offsets, uint16_t* coverage, rvn_resolve_stats* stats);
+void rvn_resolved_destroy(rvn_resolved* r);
 
 /* The identity filter loop of raven::ResolveContainedReads (RavenLib/src/construct.cc:162-217) on the per-pile overlap
  * lists overlaps[i] (concatenated, offsets[n+1], both updated in place): every overlap goes through OverlapUpdate

@@ -11,6 +11,9 @@
 // FindMedian, FindChimericRegions of every pile) on the device instead of Pile's host loops; PileT then also provides
 //   void AdoptAnnotation(std::uint32_t begin, std::uint32_t end, std::uint16_t median, bool invalid)   // cells, as Pile::begin_ / end_
 //   void AdoptChimericRegions(const std::uint32_t* pairs, std::size_t n)                                // Pile::chimeric_regions_
+//
+// raven::ResolveContainedReads and raven::ResolveChimericSequences (construct.cc:154-314) below run on the device too,
+// on the piles' host state or — the overloads that take the Pass1Handle — on the lists and coverage the pass left in HBM.
 #ifndef RAVEN_HIP_FIND_OVERLAPS_HPP_
 #define RAVEN_HIP_FIND_OVERLAPS_HPP_
 
@@ -18,6 +21,8 @@
 #include <cstdint>
 #include <iostream>
 #include <memory>
+#include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include "ram/minimizer_engine.hpp"
@@ -27,6 +32,7 @@ namespace raven {
 // the first pass's result in HBM, kept alive between FindOverlapsAndCreatePiles and TrimAndAnnotatePiles
 struct Pass1Handle {
   rvn_pass1* p = nullptr;
+  rvn_engine* engine = nullptr;  // the engine of the pass (not owned): uploads the reads for an identity filter on the pass
   Pass1Handle() = default;
   Pass1Handle(const Pass1Handle&) = delete;
   Pass1Handle& operator=(const Pass1Handle&) = delete;
@@ -56,15 +62,17 @@ void FindOverlapsAndCreatePiles(const std::shared_ptr<thread_pool::ThreadPool>& 
   struct Guard {
     rvn_pass1* p;
     Pass1Handle* keep;
+    rvn_engine* engine;
     ~Guard() {
       if (keep) {
         rvn_pass1_destroy(keep->p);
         keep->p = p;
+        keep->engine = engine;
       } else {
         rvn_pass1_destroy(p);
       }
     }
-  } guard{p, keep};
+  } guard{p, keep, minimizer_engine.handle()};
 
   const std::size_t n = sequences.size();
   std::vector<std::uint16_t> data(rvn_pass1_pile_words(p));
@@ -111,6 +119,170 @@ void TrimAndAnnotatePiles(const std::shared_ptr<thread_pool::ThreadPool>& /*thre
     piles[i]->AdoptChimericRegions(regions + 2 * static_cast<std::size_t>(roff[i]), roff[i + 1] - roff[i]);
     if (invalid[i]) std::vector<biosoup::Overlap>().swap(overlaps[i]);
   }
+}
+
+namespace detail {
+
+using ram::detail::Check;
+using ram::detail::ReadsHandle;
+using ram::detail::ToOverlap;
+
+// what rvn_resolved_fetch gives, handed to the piles and the lists: valid region, flags, remaining chimeric regions,
+// coverage, overlaps[i] (phase 2 with a median: the reference's overlaps.clear(), construct.cc:310)
+template <typename PileT>
+void AdoptResolved(rvn_resolved* r, const std::uint16_t* coverage, const std::uint64_t* coff,
+                   const std::vector<std::unique_ptr<PileT>>& piles, std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                   std::uint32_t phases) {
+  const std::size_t n = piles.size();
+  std::vector<std::uint32_t> begin(n), end(n), roff(n + 1), ooff(n + 1), regions(2 * rvn_resolved_num_regions(r));
+  std::vector<std::uint8_t> invalid(n), contained(n), chimeric(n);
+  std::vector<rvn_overlap> flat(rvn_resolved_num_overlaps(r));
+  std::vector<std::uint16_t> own(rvn_resolved_coverage_words(r));
+  std::uint16_t median = 0;
+  Check(rvn_resolved_fetch(r, begin.data(), end.data(), invalid.data(), contained.data(), chimeric.data(), regions.data(),
+                           roff.data(), &median, flat.data(), ooff.data(), own.data(), nullptr));
+  if (!coverage) coverage = own.data();
+  for (std::size_t i = 0; i < n; ++i) {
+    PileT& p = *piles[i];
+    p.AdoptCoverage(coverage + coff[i], coff[i + 1] - coff[i]);
+    p.AdoptAnnotation(begin[i], end[i], p.median(), invalid[i] != 0);
+    p.AdoptChimericRegions(regions.data() + 2 * static_cast<std::size_t>(roff[i]), roff[i + 1] - roff[i]);
+    if (contained[i]) p.set_is_contained();
+    if (chimeric[i]) p.set_is_chimeric();
+  }
+  if ((phases & 2u) && median != 0) {
+    overlaps.clear();
+    return;
+  }
+  for (std::size_t i = 0; i < n && i < overlaps.size(); ++i) {
+    overlaps[i].clear();
+    for (std::uint32_t j = ooff[i]; j < ooff[i + 1]; ++j) overlaps[i].emplace_back(ToOverlap(flat[j]));
+    if (overlaps[i].empty()) std::vector<biosoup::Overlap>().swap(overlaps[i]);
+  }
+}
+
+// the two functions on the piles' host state (rvn_resolve_contained_and_chimeric), an engine of their own on device 0
+template <typename PileT>
+void ResolveOnArrays(const std::vector<std::unique_ptr<PileT>>& piles, std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                     const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences, double identity,
+                     std::uint32_t phases) {
+  const std::size_t n = piles.size();
+  if (n == 0) return;
+  std::vector<std::uint32_t> ooff(n + 1, 0), roff(n + 1, 0), begin(n), end(n);
+  std::vector<std::uint64_t> coff(n + 1, 0);
+  for (std::size_t i = 0; i < n; ++i) {
+    ooff[i + 1] = ooff[i] + static_cast<std::uint32_t>(i < overlaps.size() ? overlaps[i].size() : 0);
+    roff[i + 1] = roff[i] + static_cast<std::uint32_t>(piles[i]->chimeric_regions().size());
+    coff[i + 1] = coff[i] + piles[i]->coverage().size();
+  }
+  std::vector<rvn_overlap> flat(ooff[n]);
+  std::vector<std::uint32_t> regions(2 * static_cast<std::size_t>(roff[n]));
+  std::vector<std::uint16_t> coverage(coff[n]), median(n);
+  std::vector<std::uint8_t> invalid(n);
+  for (std::size_t i = 0; i < n; ++i) {
+    const PileT& p = *piles[i];
+    for (std::size_t j = 0; i < overlaps.size() && j < overlaps[i].size(); ++j) {
+      const auto& o = overlaps[i][j];
+      flat[ooff[i] + j] = rvn_overlap{o.lhs_id, o.lhs_begin, o.lhs_end, o.rhs_id, o.rhs_begin, o.rhs_end, o.score, o.strand ? 1u : 0u};
+    }
+    std::size_t k = 2 * static_cast<std::size_t>(roff[i]);
+    for (const auto& reg : p.chimeric_regions()) {
+      regions[k++] = reg.first;
+      regions[k++] = reg.second;
+    }
+    std::copy(p.coverage().begin(), p.coverage().end(), coverage.begin() + coff[i]);
+    begin[i] = p.begin() >> 4;  // Pile::begin_ / end_: cells
+    end[i] = p.end() >> 4;
+    median[i] = p.median();
+    invalid[i] = p.is_invalid() ? 1 : 0;
+  }
+  struct Engine {
+    rvn_engine* e = nullptr;
+    ~Engine() { rvn_engine_destroy(e); }
+  } engine;
+  Check(rvn_engine_create(&engine.e, 15, 5, 500, 4, 100, 10000, 0));
+  ReadsHandle reads;
+  if (identity != 0 && (phases & 1u)) reads.Upload(engine.e, sequences.begin(), sequences.end());
+  rvn_resolved* r = nullptr;
+  Check(rvn_resolve_contained_and_chimeric(engine.e, reads.h, flat.data(), ooff.data(), static_cast<std::uint32_t>(n),
+                                           coverage.data(), coff.data(), regions.data(), roff.data(), begin.data(),
+                                           end.data(), median.data(), invalid.data(), identity, phases, &r));
+  struct Guard {
+    rvn_resolved* r;
+    ~Guard() { rvn_resolved_destroy(r); }
+  } guard{r};
+  AdoptResolved<PileT>(r, nullptr, coff.data(), piles, overlaps, phases);
+}
+
+// ... on the lists and the coverage the first pass left in HBM (rvn_pass1_resolve): nothing is uploaded but the reads of
+// an identity filter
+template <typename PileT>
+void ResolveOnPass(Pass1Handle& pass, const std::vector<std::unique_ptr<PileT>>& piles,
+                   std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                   const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences, double identity, std::uint32_t phases) {
+  const std::size_t n = piles.size();
+  if (n == 0 || pass.p == nullptr) return;
+  ReadsHandle reads;
+  if (identity != 0 && (phases & 1u)) {
+    if (!pass.engine) throw std::invalid_argument("[raven_hip] the identity filter on a pass needs the pass's engine");
+    reads.Upload(pass.engine, sequences.begin(), sequences.end());
+  }
+  rvn_resolved* r = nullptr;
+  Check(rvn_pass1_resolve(pass.p, reads.h, 4, identity, phases, &r));
+  struct Guard {
+    rvn_resolved* r;
+    ~Guard() { rvn_resolved_destroy(r); }
+  } guard{r};
+  std::vector<std::uint16_t> data(rvn_pass1_pile_words(pass.p));
+  std::vector<std::uint64_t> poff(n + 1);
+  Check(rvn_pass1_fetch_piles(pass.p, data.data(), poff.data()));
+  AdoptResolved<PileT>(r, data.data(), poff.data(), piles, overlaps, phases);
+}
+
+}  // namespace detail
+
+// raven::ResolveContainedReads (RavenLib/src/construct.cc:154-248, decl construct.h) with the reference's signature: the
+// identity filter loop when identity != 0, the containment marking of every overlap, contained piles made invalid with
+// their lists emptied — one C-ABI call on the piles' host state (an engine of its own on device 0, as the signature
+// names none).  overlaps[i] keeps its survivors with their updated coordinates, in order.
+// PileT must provide begin(), end(), median(), is_invalid(), set_is_contained() (raven::Pile members), the hooks
+// AdoptCoverage / AdoptAnnotation / AdoptChimericRegions of the top of this file, and
+//   const std::vector<std::uint16_t>& coverage() const                                            // Pile::data_
+//   const std::vector<std::pair<std::uint32_t, std::uint32_t>>& chimeric_regions() const         // Pile::chimeric_regions_
+//   void set_is_chimeric()                                                                        // a raven::Pile member
+template <typename PileT>
+void ResolveContainedReads(const std::vector<std::unique_ptr<PileT>>& piles,
+                           std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                           const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences,
+                           const std::shared_ptr<thread_pool::ThreadPool>& /*thread_pool*/, double identity) {
+  detail::ResolveOnArrays<PileT>(piles, overlaps, sequences, identity, 1);
+}
+// ... on the pass that FindOverlapsAndCreatePiles kept: the lists are not uploaded again
+template <typename PileT>
+void ResolveContainedReads(const std::vector<std::unique_ptr<PileT>>& piles,
+                           std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                           const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences,
+                           const std::shared_ptr<thread_pool::ThreadPool>& /*thread_pool*/, double identity,
+                           Pass1Handle& pass) {
+  detail::ResolveOnPass<PileT>(pass, piles, overlaps, sequences, identity, 1);
+}
+
+// raven::ResolveChimericSequences (RavenLib/src/construct.cc:250-314) with the reference's signature: the global median,
+// Pile::ClearChimericRegions of every valid pile, the last OverlapUpdate / containment sweep, overlaps.clear().
+// PileT: as for ResolveContainedReads, and set_is_invalid() is not needed (AdoptAnnotation carries the flag).
+template <typename PileT>
+void ResolveChimericSequences(const std::shared_ptr<thread_pool::ThreadPool>& /*thread_pool*/,
+                              const std::vector<std::unique_ptr<PileT>>& piles,
+                              std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                              const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences) {
+  detail::ResolveOnArrays<PileT>(piles, overlaps, sequences, 0, 2);
+}
+template <typename PileT>
+void ResolveChimericSequences(const std::shared_ptr<thread_pool::ThreadPool>& /*thread_pool*/,
+                              const std::vector<std::unique_ptr<PileT>>& piles,
+                              std::vector<std::vector<biosoup::Overlap>>& overlaps,
+                              const std::vector<std::unique_ptr<biosoup::NucleicAcid>>& sequences, Pass1Handle& pass) {
+  detail::ResolveOnPass<PileT>(pass, piles, overlaps, sequences, 0, 2);
 }
 
 // raven::FindOverlapsAndRepetetiveRegions (RavenLib/src/construct.cc:316-491, decl construct.h:49-54) with the

@@ -103,6 +103,8 @@ struct StageTimes {
 };
 
 struct PileState;
+struct PileRegion;
+struct ResolveState;
 
 // Tuning a deployment may set (rvn_engine_set_option; 0 = the built-in default everywhere).  None of them changes a result.
 struct EngineOptions {
@@ -229,6 +231,22 @@ struct Engine {
   u64 polish_chunk_windows = 16384;  // windows per POA chunk of a polishing round (0 = everything in one batch)
   PileState* pile_pool = nullptr;  // buffers of the last destroyed pass, adopted by the next one (engine.hip)
   std::shared_ptr<int> life = std::make_shared<int>(0);  // lets handles notice that their engine is gone
+};
+
+// The per-site kernel timers of the engine count the launches of the entry point that holds one of these
+struct UseTimers {
+  explicit UseTimers(Engine& e) {
+    e.ktimers.stream = e.stream;
+    // Fold the event pairs of the previous entry point into the per-site sums now (the stream is idle between entry
+    // points): the events are reused instead of growing the pool by two hipEventCreate per launch, which cost more
+    // than the launches themselves on a slow host (0.5 s per pass at C4).
+    if (e.ktimers.enabled && !e.ktimers.recs.empty()) {
+      (void)rvn_stream_sync(e.stream);
+      e.ktimers.resolve();
+    }
+    g_kernel_timers = &e.ktimers;
+  }
+  ~UseTimers() { g_kernel_timers = nullptr; }
 };
 
 // Hands every scratch / intermediate buffer of the engine back to the allocator (index, sketches, last Map result,
@@ -404,6 +422,38 @@ void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_
 void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u64 O, const u32* h_begin, const u32* h_end,
                            const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd);
 void identity_filter_compact(Overlap* h_ovl, u32* h_off, u32 n, const u8* ok, const Overlap* upd);
+// OverlapUpdate + [identity != 0: the edit-distance score] on a list in HBM, in place: ok flags out.  regions by read id,
+// index_of: id -> index in r (both unused when identity == 0, where this is update_kernel alone)
+void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, const PileRegion* d_regions,
+                         const u32* d_index_of, double identity, u8* d_ok);
+// compact_kernel: out[slot[i]] = in[i] where keep[i]
+void compact_overlaps(Engine& e, const Overlap* d_in, const u8* d_keep, const u32* d_slot, u64 n, Overlap* d_out);
+
+// ResolveContainedReads / ResolveChimericSequences on the device (resolve.hip): the piles' state and the per-pile
+// overlap lists in HBM between and after the two phases
+struct ResolveStats {  // == rvn_resolve_stats
+  u64 dropped_by_update[2] = {0, 0};  // overlaps OverlapUpdate dropped in the marking loop of phase 1 / in phase 2
+  u64 dropped_by_filter = 0;          // overlaps the identity filter loop dropped (OverlapUpdate or the score)
+  u64 dropped_by_containment = 0;     // type 1 / 2 overlaps of phase 1 that marked a pile
+  u32 contained[2] = {0, 0};          // piles that became contained in phase 1 / phase 2
+  u32 cut = 0, invalidated = 0;       // piles ClearChimericRegions cut / made invalid
+};
+struct ResolveState {
+  u32 n = 0;
+  u32 phases_done = 0;
+  DevBuf begin, end, median, invalid, contained, chimeric;  // u32 cells, u32 cells, u16, u8, u8, u8 per pile
+  DevBuf pr;                                                // PileRegion[n]: begin / end in bases + invalid
+  DevBuf roff, rcount, regions;  // chimeric regions: slots of pile i at roff[i] (u32[n + 1]), rcount[i] of them in use
+  u32 regions_total = 0;         // slots
+  DevBuf ovl, off;               // Overlap[n_overlaps], u32[n + 1]
+  u64 n_overlaps = 0;
+  DevBuf own_cov, own_cov_off;  // the host-array form's coverage (the resident form works on PileState::pile_data)
+  u16* cov = nullptr;
+  const u64* cov_off = nullptr;
+  u64 cov_words = 0;
+  u16 global_median = 0;
+  ResolveStats stats;
+};
 
 // Pass-1 state: per-pile kept overlaps + coverage (pile.hip)
 struct PileState {
@@ -415,6 +465,10 @@ struct PileState {
   DevBuf kept;       // Overlap[kept_total]
   u64 kept_total = 0;
   DevBuf new_off, new_list, tmp1, tmp2, tmp3, tmp4, tmp5, tmp6;
+  // TrimAndAnnotatePiles' result per pile, kept in HBM for the stages behind it (resolve.hip)
+  DevBuf ann_begin, ann_end, ann_median, ann_invalid;  // u32[n] cells, u32[n] cells, u16[n], u8[n]
+  bool trimmed = false;
+  std::shared_ptr<ResolveState> resolve;  // what rvn_pass1_resolve left on this pass (resolve.hip)
 };
 void piles_init(Engine& e, const ReadsDev& r, PileState& ps);
 void piles_merge(Engine& e, const ReadsDev& r, const MapOut& mo, u32 kmax, PileState& ps);
@@ -423,6 +477,8 @@ void piles_trim_and_median(Engine& e, PileState& ps, u32 coverage, u32* h_begin,
 // Pile::FindChimericRegions of every valid pile on the coverage in HBM (pile.hip): CSR of (begin, end) cell pairs
 void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, std::vector<u32>& h_off,
                                  std::vector<u32>& h_regions);
+// the same with the flags and the result in HBM: d_roff[n + 1], regions = (begin, end) pairs; returns the number of pairs
+u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_invalid, DevBuf& roff, DevBuf& regions);
 // Pile::AddKmers for reads [first_read, first_read + n_reads) (pile.hip)
 void pile_add_kmers_batch(Engine& e, const ReadsDev& r, const u32* h_pos, const u64* h_pos_off, u32 n_reads,
                           u32 first_read, u8* h_out, const u64* h_out_off);
@@ -455,6 +511,23 @@ struct rvn_engine {
 struct rvn_reads {
   rvn::ReadsDev r;
   std::vector<std::string> names;  // rvn_reads_load: the sequences' names
+};
+// The pile buffers (coverage, kept lists, merge scratch: a dozen allocations) are recycled through the engine:
+// destroying a pass hands them back, the next pass adopts them, so steady-state passes do not touch the allocator.
+struct rvn_pass1 {
+  rvn::Engine* e = nullptr;
+  std::unique_ptr<rvn::PileState> state;
+  rvn::PileState& ps;
+  std::weak_ptr<int> engine_life;  // a handle may outlive its engine (e.g. interpreter teardown order)
+  std::unique_ptr<rvn::ReadsDev> meta;  // sharded pass: lengths / ids of ALL reads (piles need no bases)
+  explicit rvn_pass1(rvn::Engine& eng)
+      : e(&eng), state(eng.pile_pool ? eng.pile_pool : new rvn::PileState()), ps(*state), engine_life(eng.life) {
+    eng.pile_pool = nullptr;
+  }
+  ~rvn_pass1() {
+    ps.resolve.reset();  // the resolved state is the pass's, not the pool's (a result handle may still share it)
+    if (!engine_life.expired() && !e->pile_pool) e->pile_pool = state.release();
+  }
 };
 struct rvn_pass2 {
   rvn::Engine* e = nullptr;

@@ -30,23 +30,6 @@ using namespace rvn;
 
 static_assert(sizeof(rvn_overlap) == sizeof(rvn::Overlap), "overlap layout");
 
-// The pile buffers (coverage, kept lists, merge scratch: a dozen allocations) are recycled through the engine:
-// destroying a pass hands them back, the next pass adopts them, so steady-state passes do not touch the allocator.
-struct rvn_pass1 {
-  Engine* e = nullptr;
-  std::unique_ptr<PileState> state;
-  PileState& ps;
-  std::weak_ptr<int> engine_life;  // a handle may outlive its engine (e.g. interpreter teardown order)
-  std::unique_ptr<ReadsDev> meta;  // sharded pass: lengths / ids of ALL reads (piles need no bases)
-  explicit rvn_pass1(Engine& eng)
-      : e(&eng), state(eng.pile_pool ? eng.pile_pool : new PileState()), ps(*state), engine_life(eng.life) {
-    eng.pile_pool = nullptr;
-  }
-  ~rvn_pass1() {
-    if (!engine_life.expired() && !e->pile_pool) e->pile_pool = state.release();
-  }
-};
-
 namespace {
 
 thread_local std::string g_err;
@@ -123,21 +106,6 @@ namespace {
 const char* kStageNames[StageTimes::kNum] = {"sketch", "sort", "index", "filter", "query_sketch", "match",
                                              "seg_sort", "intervals", "chain", "compact", "merge", "pile",
                                              "truncate"};
-
-struct UseTimers {
-  explicit UseTimers(Engine& e) {
-    e.ktimers.stream = e.stream;
-    // Fold the event pairs of the previous entry point into the per-site sums now (the stream is idle between entry
-    // points): the events are reused instead of growing the pool by two hipEventCreate per launch, which cost more
-    // than the launches themselves on a slow host (0.5 s per pass at C4).
-    if (e.ktimers.enabled && !e.ktimers.recs.empty()) {
-      (void)rvn_stream_sync(e.stream);
-      e.ktimers.resolve();
-    }
-    g_kernel_timers = &e.ktimers;
-  }
-  ~UseTimers() { g_kernel_timers = nullptr; }
-};
 
 int fetch_values(Engine& e, const DevBuf& val, u64 n, uint64_t* values);
 

@@ -190,6 +190,14 @@ u64 compact(Engine& e, DevBuf& list, u64 n, const u8* d_keep, DevBuf& tmp_slot, 
   return m;
 }
 
+}  // namespace
+
+void compact_overlaps(Engine& e, const Overlap* d_in, const u8* d_keep, const u32* d_slot, u64 n, Overlap* d_out) {
+  if (n == 0) return;
+  compact_kernel<<<div_up(n, 256), 256, 0, e.stream>>>(d_in, d_keep, d_slot, n, d_out);
+  RVN_LAUNCH_CHECK();
+}
+
 // OverlapUpdate + [identity] on a device list; ok flags out.  regions indexed by read id, index_of: id -> index in r.
 void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, const PileRegion* d_regions,
                          const u32* d_index_of, double identity, u8* d_ok) {
@@ -212,6 +220,8 @@ void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, co
   identity_keep_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, d_ok, d_slot, n, d_dist, identity);
   RVN_LAUNCH_CHECK();
 }
+
+namespace {
 
 PileRegion* upload_regions(Engine& e, const u32* h_begin, const u32* h_end, const u8* h_invalid, u32 n) {
   std::vector<PileRegion> reg(n);

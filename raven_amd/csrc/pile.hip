@@ -200,6 +200,8 @@ void piles_init(Engine& e, const ReadsDev& r, PileState& ps) {
   RVN_HIP(hipMemsetAsync(ko, 0, (static_cast<size_t>(r.n) + 1) * 4, e.stream));
   ps.kept.reserve(64);
   ps.kept_total = 0;
+  ps.trimmed = false;
+  ps.resolve.reset();
   RVN_HIP(rvn_stream_sync(e.stream));  // `off` is a stack-owned host buffer
 }
 
@@ -446,10 +448,11 @@ void piles_trim_and_median(Engine& e, PileState& ps, u32 coverage, u32* h_begin,
   const u32 n = ps.n;
   if (n == 0) return;
   hipStream_t s = e.stream;
-  u32* d_begin = e.tmp_a.get<u32>(static_cast<size_t>(n) + 1);
-  u32* d_end = e.tmp_b.get<u32>(static_cast<size_t>(n) + 1);
-  u16* d_med = e.tmp_c.get<u16>(static_cast<size_t>(n) + 1);
-  u8* d_inv = e.tmp_d.get<u8>(static_cast<size_t>(n) + 1);
+  // the result stays with the pass (ResolveContainedReads / ResolveChimericSequences read it there: resolve.hip)
+  u32* d_begin = ps.ann_begin.get<u32>(static_cast<size_t>(n) + 1);
+  u32* d_end = ps.ann_end.get<u32>(static_cast<size_t>(n) + 1);
+  u16* d_med = ps.ann_median.get<u16>(static_cast<size_t>(n) + 1);
+  u8* d_inv = ps.ann_invalid.get<u8>(static_cast<size_t>(n) + 16);
   RVN_KLAUNCH(kKPileTrim, pile_trim_kernel<<<div_up(n, 4), 256, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), n,
                                                                        coverage, 1260u >> kPSS, d_begin, d_end, d_med, d_inv));
   if (h_begin) RVN_HIP(hipMemcpyAsync(h_begin, d_begin, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, s));
@@ -457,6 +460,7 @@ void piles_trim_and_median(Engine& e, PileState& ps, u32 coverage, u32* h_begin,
   if (h_median) RVN_HIP(hipMemcpyAsync(h_median, d_med, static_cast<size_t>(n) * 2, hipMemcpyDeviceToHost, s));
   if (h_invalid) RVN_HIP(hipMemcpyAsync(h_invalid, d_inv, static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
+  ps.trimmed = true;
 }
 
 
@@ -624,6 +628,43 @@ __global__ void chimeric_gather_kernel(const u32* __restrict__ out_tmp, const u6
 }
 }  // namespace
 
+// d_invalid: the piles' is_invalid flags (from piles_trim_and_median) in HBM; the CSR stays there: roff = u32[n + 1],
+// regions = (begin, end) cell pairs.  Returns the number of pairs.
+u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, DevBuf& roff, DevBuf& regions) {
+  hipStream_t s = e.stream;
+  const u32 n = ps.n;
+  u32* d_roff = roff.get<u32>(static_cast<size_t>(n) + 2);
+  if (n == 0 || ps.pile_words == 0) {
+    RVN_HIP(hipMemsetAsync(d_roff, 0, (static_cast<size_t>(n) + 1) * 4, s));
+    regions.get<u32>(2);
+    RVN_HIP(rvn_stream_sync(s));
+    return 0;
+  }
+  SlopeRegion* d_slopes = e.tmp_b.get<SlopeRegion>(2 * ps.pile_words + 2);
+  u16* d_tmp = e.tmp_c.get<u16>(ps.pile_words + 1);
+  u32* d_out = e.tmp_d.get<u32>(2 * ps.pile_words + 4);
+  u32* d_cnt = e.tmp_e.get<u32>(static_cast<size_t>(n) + 16);
+  u32* d_ovf = d_cnt + n + 8;
+  RVN_HIP(hipMemsetAsync(d_ovf, 0, 4, s));
+  if (knob("RVN_CHIMERIC_PER_THREAD"))  // (the earlier layout: one thread per pile; kept for comparisons)
+    RVN_KLAUNCH(kKPileTrim, pile_chimeric_kernel<<<div_up(n, 64), 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
+                                                                             d_slopes, d_tmp, d_out, d_cnt, d_ovf));
+  else
+    RVN_KLAUNCH(kKPileTrim, pile_chimeric_wave_kernel<<<n, 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
+                                                                      d_slopes, d_tmp, d_out, d_cnt, d_ovf));
+  exclusive_scan_u32_u32(d_cnt, d_roff, n, e.scan_tmp, s);
+  RVN_HIP(hipMemcpyAsync(e.h_pin + 1, d_roff + n, 4, hipMemcpyDeviceToHost, s));
+  if (read_back(e, d_ovf, 4) != 0)
+    throw HipError("[raven_hip] FindChimericRegions: a pile produced more than two slope regions per cell (internal error: the bound in pile.hip is a proof)");
+  const u32 total = static_cast<u32>(e.h_pin[1]);
+  u32* d_regions = regions.get<u32>(2ULL * total + 2);
+  if (total) {
+    chimeric_gather_kernel<<<div_up(n, 256), 256, 0, s>>>(d_out, ps.pile_off.as<u64>(), d_cnt, d_roff, n, d_regions);
+    RVN_LAUNCH_CHECK();
+  }
+  return total;
+}
+
 // h_invalid: the piles' is_invalid flags (from piles_trim_and_median); h_off[n + 1] / regions: CSR of (begin, end) cell pairs
 void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, std::vector<u32>& h_off,
                                  std::vector<u32>& h_regions) {
@@ -634,33 +675,11 @@ void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, 
   if (n == 0 || ps.pile_words == 0) return;
   u8* d_inv = e.tmp_a.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemcpyAsync(d_inv, h_invalid, n, hipMemcpyHostToDevice, s));
-  SlopeRegion* d_slopes = e.tmp_b.get<SlopeRegion>(2 * ps.pile_words + 2);
-  u16* d_tmp = e.tmp_c.get<u16>(ps.pile_words + 1);
-  u32* d_out = e.tmp_d.get<u32>(2 * ps.pile_words + 4);
-  u32* d_cnt = e.tmp_e.get<u32>(2 * static_cast<size_t>(n) + 8);
-  u32* d_roff = d_cnt + n + 1;
-  u32* d_ovf = e.tmp_f.get<u32>(4);
-  RVN_HIP(hipMemsetAsync(d_ovf, 0, 4, s));
-  if (knob("RVN_CHIMERIC_PER_THREAD"))  // (the earlier layout: one thread per pile; kept for comparisons)
-    RVN_KLAUNCH(kKPileTrim, pile_chimeric_kernel<<<div_up(n, 64), 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
-                                                                             d_slopes, d_tmp, d_out, d_cnt, d_ovf));
-  else
-    RVN_KLAUNCH(kKPileTrim, pile_chimeric_wave_kernel<<<n, 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
-                                                                      d_slopes, d_tmp, d_out, d_cnt, d_ovf));
-  exclusive_scan_u32_u32(d_cnt, d_roff, n, e.scan_tmp, s);
-  RVN_HIP(hipMemcpyAsync(h_off.data(), d_roff, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToHost, s));
-  if (read_back(e, d_ovf, 4) != 0)
-    throw HipError("[raven_hip] FindChimericRegions: a pile produced more than two slope regions per cell (internal error: the bound in pile.hip is a proof)");
-  RVN_HIP(rvn_stream_sync(s));
-  const u32 total = h_off[n];
+  const u32 total = piles_find_chimeric_regions_dev(e, ps, d_inv, e.tmp_f, e.sort_tmp);
+  RVN_HIP(hipMemcpyAsync(h_off.data(), e.tmp_f.ptr, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToHost, s));
   h_regions.assign(2ULL * total, 0);
-  if (total) {
-    u32* d_regions = e.sort_tmp.get<u32>(2ULL * total + 2);
-    chimeric_gather_kernel<<<div_up(n, 256), 256, 0, s>>>(d_out, ps.pile_off.as<u64>(), d_cnt, d_roff, n, d_regions);
-    RVN_LAUNCH_CHECK();
-    RVN_HIP(hipMemcpyAsync(h_regions.data(), d_regions, 2ULL * total * 4, hipMemcpyDeviceToHost, s));
-    RVN_HIP(rvn_stream_sync(s));
-  }
+  if (total) RVN_HIP(hipMemcpyAsync(h_regions.data(), e.sort_tmp.ptr, 2ULL * total * 4, hipMemcpyDeviceToHost, s));
+  RVN_HIP(rvn_stream_sync(s));
 }
 
 }  // namespace rvn

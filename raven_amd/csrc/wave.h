@@ -44,6 +44,16 @@ __device__ __forceinline__ T wave_max(T v) {
   return v;
 }
 
+template <typename T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    T o = __shfl_xor(v, off, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
 // Inclusive max-scan.
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_max(T v) {

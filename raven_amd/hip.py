@@ -56,6 +56,8 @@ SYMBOLS = [
     "rvn_polish_output_as_reads", "rvn_group_find_overlaps_and_repetitive_regions", "rvn_group_filter_overlaps_by_identity",
     "rvn_resolve_repeat_induced_overlaps", "rvn_repeats_num_overlaps", "rvn_repeats_num_regions", "rvn_repeats_fetch",
     "rvn_repeats_destroy",
+    "rvn_pass1_resolve", "rvn_resolve_contained_and_chimeric", "rvn_resolved_num_overlaps", "rvn_resolved_num_regions",
+    "rvn_resolved_coverage_words", "rvn_resolved_fetch", "rvn_resolved_destroy",
 ]
 
 # TEST INFRASTRUCTURE: what include/raven_hip_test.h declares on top (libraven_hip_test.so only)
@@ -334,10 +336,56 @@ class Reads:
             pass
 
 
+def _fetch_resolved(h, n):
+    """rvn_resolved_fetch of everything, then rvn_resolved_destroy: the dict Pass1.resolve and
+    Engine.resolve_contained_and_chimeric return."""
+    L = lib()
+    vp, u64 = C.c_void_p, C.c_uint64
+    for f in (L.rvn_resolved_num_overlaps, L.rvn_resolved_num_regions, L.rvn_resolved_coverage_words):
+        f.argtypes = [vp]
+        f.restype = u64
+    L.rvn_resolved_fetch.argtypes = [vp] * 13
+    L.rvn_resolved_destroy.argtypes = [vp]
+    try:
+        begin, end = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        invalid, contained, chimeric = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        reg = np.zeros((int(L.rvn_resolved_num_regions(h)), 2), dtype=np.uint32)
+        roff = np.zeros(n + 1, dtype=np.uint32)
+        median = np.zeros(1, dtype=np.uint16)
+        ovl = np.zeros(int(L.rvn_resolved_num_overlaps(h)), dtype=OVERLAP_DTYPE)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        words = int(L.rvn_resolved_coverage_words(h))
+        cov = np.zeros(words, dtype=np.uint16)
+        stats = np.zeros(6, dtype=np.uint64)  # rvn_resolve_stats: 4 x u64, 4 x u32
+        _check(L.rvn_resolved_fetch(h, _p(begin), _p(end), _p(invalid), _p(contained), _p(chimeric), _p(reg), _p(roff),
+                                    _p(median), _p(ovl), _p(off), _p(cov), _p(stats)))
+    finally:
+        L.rvn_resolved_destroy(h)
+    s32 = stats[4:].view(np.uint32)
+    return dict(begin=begin, end=end, invalid=invalid, contained=contained, chimeric=chimeric, regions=reg,
+                region_offsets=roff, median=int(median[0]), overlaps=ovl, offsets=off, coverage=cov,
+                stats=dict(dropped_by_update=(int(stats[0]), int(stats[1])), dropped_by_filter=int(stats[2]),
+                           dropped_by_containment=int(stats[3]), contained=(int(s32[0]), int(s32[1])), cut=int(s32[2]),
+                           invalidated=int(s32[3])))
+
+
 class Pass1:
     def __init__(self, h, n):
         self._h = h
         self.n = n
+
+    def resolve(self, reads=None, identity=0.0, coverage=4, phases=3):
+        """raven::ResolveContainedReads (phases & 1) and raven::ResolveChimericSequences (phases & 2) on the lists and the
+        coverage of this pass in HBM (rvn_pass1_resolve); TrimAndAnnotatePiles(coverage) first when it has not run yet.
+        Returns dict(begin, end (cells), invalid, contained, chimeric, regions ((k, 2) cells), region_offsets[n + 1],
+        median (the global one of phase 2), overlaps, offsets[n + 1] (after the last phase that ran), coverage (empty:
+        it stays on the pass, see piles()), stats)."""
+        L = lib()
+        h = C.c_void_p()
+        L.rvn_pass1_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
+        _check(L.rvn_pass1_resolve(self._h, reads._h if reads is not None else None, int(coverage), float(identity),
+                                   int(phases), C.byref(h)))
+        return _fetch_resolved(h, self.n)
 
     def piles(self):
         L = lib()
@@ -853,6 +901,35 @@ class Engine:
             L.rvn_repeats_destroy(h)
         return dict(overlaps=ovl, regions=reg, region_offsets=roff, is_repetitive=isrep,
                     iterations=int(stats[0]) & 0xFFFFFFFF, components=int(stats[0]) >> 32, removed=int(stats[1]))
+
+    def resolve_contained_and_chimeric(self, overlaps, offsets, coverage, coverage_offsets, regions, region_offsets, begin,
+                                       end, median, invalid, reads=None, identity=0.0, phases=3):
+        """The stage of Pass1.resolve on host arrays (rvn_resolve_contained_and_chimeric): lists + offsets[n + 1] as
+        Pass1.overlaps() gives them, coverage + offsets as Pass1.piles(), regions ((k, 2) cells) + region_offsets[n + 1],
+        begin / end in cells, median, invalid 0/1.  Returns the same dict, with the coverage."""
+        o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        cov = np.ascontiguousarray(coverage, dtype=np.uint16)
+        coff = np.ascontiguousarray(coverage_offsets, dtype=np.uint64)
+        reg = np.ascontiguousarray(regions, dtype=np.uint32).reshape(-1)
+        roff = np.ascontiguousarray(region_offsets, dtype=np.uint32)
+        b = np.ascontiguousarray(begin, dtype=np.uint32)
+        en = np.ascontiguousarray(end, dtype=np.uint32)
+        med = np.ascontiguousarray(median, dtype=np.uint16)
+        inv = np.ascontiguousarray(invalid, dtype=np.uint8)
+        n = b.shape[0]
+        assert en.shape[0] == n and med.shape[0] == n and inv.shape[0] == n
+        assert off.shape[0] == n + 1 == coff.shape[0] == roff.shape[0]
+        assert o.shape[0] == int(off[-1]) and cov.shape[0] == int(coff[-1]) and reg.shape[0] == 2 * int(roff[-1])
+        h = C.c_void_p()
+        L = lib()
+        vp = C.c_void_p
+        L.rvn_resolve_contained_and_chimeric.argtypes = [vp, vp, vp, vp, C.c_uint32] + [vp] * 8 + [C.c_double, C.c_uint32,
+                                                                                                C.POINTER(vp)]
+        _check(L.rvn_resolve_contained_and_chimeric(self._h, reads._h if reads is not None else None, _p(o), _p(off), n,
+                                                    _p(cov), _p(coff), _p(reg), _p(roff), _p(b), _p(en), _p(med), _p(inv),
+                                                    float(identity), int(phases), C.byref(h)))
+        return _fetch_resolved(h, n)
 
     def filter_overlaps_by_identity(self, reads: Reads, overlaps, offsets, pile_begin, pile_end, pile_invalid, identity):
         """Identity filter loop of ResolveContainedReads on per-pile lists: returns (overlaps, offsets) filtered."""
