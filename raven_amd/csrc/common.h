@@ -28,7 +28,7 @@ struct HipError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
 // hipMalloc failed with the block pool already empty: the stage entry points hand back every scratch buffer of the
-// engine and run the stage once more before they report it (engine.hip: guarded)
+// engine and run the stage once more before they report it (abi.h: guarded)
 struct DeviceOutOfMemory : HipError {
   using HipError::HipError;
 };
@@ -63,7 +63,7 @@ inline const char* knob(const char* name) {
 // MI355X (17 GB: 0.64 s; a traced step spent 14 s in three such calls).  With the arena that traffic is a first-fit
 // search in a free list: one hipMalloc of (free memory - margin) when it starts, no driver call afterwards; a request
 // the arena cannot hold falls through to the driver, and if that is out of memory too the stage entry point releases
-// every scratch buffer and runs the stage once more (engine.hip: guarded).  Implemented in engine.hip.
+// every scratch buffer and runs the stage once more (abi.h: guarded).  Implemented in devpool.hip.
 namespace devpool {
 bool active();                 // an arena exists on the current device
 bool start(size_t bytes);      // one hipMalloc; false if the driver refuses

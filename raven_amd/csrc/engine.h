@@ -1,9 +1,7 @@
 // engine.h — internal structures of the MI355X overlap engine (not part of the public C ABI).
 #pragma once
 
-#include <string>
 #include <atomic>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -103,7 +101,7 @@ struct StageTimes {
 };
 
 struct PileState;
-struct PileRegion;
+struct PileRegion;  // overlap_rules.h
 struct ResolveState;
 
 // Tuning a deployment may set (rvn_engine_set_option; 0 = the built-in default everywhere).  None of them changes a result.
@@ -229,7 +227,7 @@ struct Engine {
   HostBuf host_big;      // ... and the unpinned one for larger ones
   PinBuf pin_out;        // pinned consensus buffer of the POA chunk in flight
   u64 polish_chunk_windows = 16384;  // windows per POA chunk of a polishing round (0 = everything in one batch)
-  PileState* pile_pool = nullptr;  // buffers of the last destroyed pass, adopted by the next one (engine.hip)
+  PileState* pile_pool = nullptr;  // buffers of the last destroyed pass, adopted by the next one (rvn_pass1 below)
   std::shared_ptr<int> life = std::make_shared<int>(0);  // lets handles notice that their engine is gone
 };
 
@@ -357,7 +355,6 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& R, std::vector
 // the same code stepped on the CPU (64 emulated lanes): test hook, see rvn_test_nw_breakpoints
 int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r_len, u32 t_begin, u32 n, u32 q_begin, u32 m,
                         int rc, u32 w, u32 k, int force_R, NwWindowRec* recs, u32* distance, u32* band);
-// One racon polishing round (polish.hip): targets T, reads R, optional per-base Phred+33 qualities of the reads
 // shard.hip — partition / regroup steps of the sharded pass, all pointers device pointers unless noted
 void shard_split_minimizers(Engine& e, const u64* d_val, const u64* d_org, u64 n, u32 world, u64* d_val_out, u64* d_org_out,
                             u64* counts /* host [world] */);
@@ -368,6 +365,7 @@ void shard_adjacent_diff(Engine& e, const u64* d_seg, u64 n, u64* d_cnt);
 void shard_regroup(Engine& e, u32 world, const u64* const* d_cnt, const u64* const* d_grp, const u64* const* d_pos,
                    const u64* n_src /* host */, u32 n_reads, u64* d_seg, u64* d_grp_out, u64* d_pos_out);
 void shard_lhs_offsets(Engine& e, const Overlap* d_ovl, u64 n, u32 n_reads, u32* d_off);
+// One racon polishing round (polish.hip): targets T, reads R, optional per-base Phred+33 qualities of the reads
 // polish_round's consensus straight into the caller's buffer (target t at out + off[t], at most off[t + 1] - off[t] bytes;
 // len[t] = its length) instead of into `polished` (which then stays empty): one pass over the 100 MB of a C4 round less
 struct PolishDirectOut {
@@ -393,13 +391,15 @@ struct Pass2State {
   std::vector<u64> h_kmers_off;
   u64 kmers_total = 0;
 };
-// ram::MinimizerEngine::Minimize(first, last, minhash) on a read set (engine.hip)
-void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool minhash);
+// ram::MinimizerEngine::Minimize(first, last, minhash) on a read set (engine.hip).  With prefetch_query the minhash QUERY
+// sketch of the same range is derived from the same raw sketch, so map_batch over that range does not sketch again.
+void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool minhash, bool prefetch_query = false);
+// minimizer values of a sketch or an index to the host as u64, whatever their width on the device (engine.hip)
+void fetch_values(Engine& e, const DevBuf& val, u64 n, u64* values);
 void reads_subset(Engine& e, const ReadsDev& R, const std::vector<u32>& src, ReadsDev& V);
 void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid, double freq,
                  u32 kmer_len, double identity, u64 batch_bases, Pass2State& out);
 // The stages of second_pass, also driven per rank by the device group (group.hip)
-struct PileRegion;
 struct Pass2Prep {
   std::vector<u32> valid;                       // ids of the valid reads, ascending
   u32 sv = 0;                                   // valid reads that are mapped (0: every pile valid, construct.cc:343-349)
@@ -494,17 +494,13 @@ struct RepeatResult {
   u32 iterations = 0, components = 0;
   u64 removed = 0;
 };
-// a stage entry point's body under the engine's lock and error handling (engine.hip guarded(): HIP errors, host memory,
-// invalid arguments, and one rerun from released scratch when the device runs out of memory)
-int engine_guarded(Engine* e, const std::function<int()>& f);
-void set_last_error(const std::string& msg);
 void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32 n, const u16* h_cov, const u64* h_cov_off,
                                      const u8* h_kmers, const u64* h_kmer_off, const u32* h_begin, const u32* h_end,
                                      const u16* h_median, const u8* h_invalid, RepeatResult& res);
 
 }  // namespace rvn
 
-// Handles of the C ABI (include/raven_hip.h) that engine.hip and group.hip both look into
+// Handles of the C ABI (include/raven_hip.h) that several translation units look into
 struct rvn_engine {
   rvn::Engine e;
 };

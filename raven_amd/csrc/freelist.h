@@ -1,5 +1,5 @@
 // freelist.h — first-fit free list over the offsets [0, size) of one block of memory: the bookkeeping of the device arena
-// (engine.hip: devpool).  Offsets and lengths only, no memory behind it, so the CPU suite can drive it
+// (devpool.hip).  Offsets and lengths only, no memory behind it, so the CPU suite can drive it
 // (rvn_test_freelist, tests/test_freelist.py).  Blocks are multiples of `grain`; free neighbours are coalesced.
 #ifndef RVN_FREELIST_H_
 #define RVN_FREELIST_H_

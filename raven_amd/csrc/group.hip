@@ -22,12 +22,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/raven_hip.h"
-#include "engine.h"
-
-namespace rvn {
-void set_last_error(const std::string& msg);  // engine.hip: the calling thread's rvn_last_error()
-}
+#include "abi.h"
 
 using rvn::DevBuf;
 using rvn::u32;

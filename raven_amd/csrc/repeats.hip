@@ -17,8 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/raven_hip.h"
-#include "engine.h"
+#include "abi.h"
 #include "overlap_rules.h"
 #include "repeats.h"
 #include "wave.h"
@@ -495,13 +494,6 @@ void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32
 // ---- C ABI (include/raven_hip.h) -----------------------------------------------------------------------------------
 using namespace rvn;
 
-namespace {
-int fail_inval(const char* msg) {
-  set_last_error(msg);
-  return RVN_EINVAL;
-}
-}  // namespace
-
 struct rvn_repeats {
   RepeatResult res;
 };
@@ -510,23 +502,23 @@ int rvn_resolve_repeat_induced_overlaps(rvn_engine* h, const rvn_overlap* overla
                                         const uint16_t* coverage, const uint64_t* coverage_offsets, const uint8_t* kmers,
                                         const uint64_t* kmers_offsets, const uint32_t* pile_begin, const uint32_t* pile_end,
                                         const uint16_t* median, const uint8_t* invalid, rvn_repeats** out) {
-  return engine_guarded(h ? &h->e : nullptr, [&]() -> int {
+  return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h || !out || (n_overlaps && !overlaps) || !coverage_offsets || !kmers_offsets ||
         (n_piles && (!pile_begin || !pile_end || !median || !invalid)) ||
         (coverage_offsets[n_piles] && !coverage) || (kmers_offsets[n_piles] && !kmers))
-      return fail_inval("[raven_hip] rvn_resolve_repeat_induced_overlaps: NULL argument");
+      return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: NULL argument");
     *out = nullptr;
     if (coverage_offsets[0] != 0 || kmers_offsets[0] != 0)
-      return fail_inval("[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must start at 0");
+      return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must start at 0");
     for (u32 i = 0; i < n_piles; ++i) {
       if (coverage_offsets[i + 1] < coverage_offsets[i] || kmers_offsets[i + 1] < kmers_offsets[i])
-        return fail_inval("[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must not decrease");
+        return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must not decrease");
       if (coverage_offsets[i + 1] - coverage_offsets[i] >= (1u << 27) || kmers_offsets[i + 1] - kmers_offsets[i] >= (1u << 27))
-        return fail_inval("[raven_hip] rvn_resolve_repeat_induced_overlaps: a pile of 2^27 cells or more");
+        return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: a pile of 2^27 cells or more");
     }
     for (u64 x = 0; x < n_overlaps; ++x)
       if (overlaps[x].lhs_id >= n_piles || overlaps[x].rhs_id >= n_piles)
-        return fail_inval("[raven_hip] rvn_resolve_repeat_induced_overlaps: overlap of an unknown pile");
+        return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: overlap of an unknown pile");
     Engine& e = h->e;
     RVN_HIP(hipSetDevice(e.device));
     std::unique_ptr<rvn_repeats> r(new rvn_repeats());
@@ -542,7 +534,7 @@ uint64_t rvn_repeats_num_regions(const rvn_repeats* r) { return r ? r->res.reg.s
 
 int rvn_repeats_fetch(const rvn_repeats* r, rvn_overlap* overlaps, uint32_t* regions, uint32_t* region_offsets,
                       uint8_t* is_repetitive, rvn_repeats_stats* stats) {
-  if (!r) return fail_inval("[raven_hip] NULL repeats result");
+  if (!r) return fail(RVN_EINVAL, "[raven_hip] NULL repeats result");
   const RepeatResult& x = r->res;
   if (overlaps && !x.ovl.empty()) std::memcpy(overlaps, x.ovl.data(), x.ovl.size() * sizeof(Overlap));
   if (regions && !x.reg.empty()) std::memcpy(regions, x.reg.data(), x.reg.size() * 4);

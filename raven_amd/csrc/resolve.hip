@@ -19,9 +19,8 @@
 #include <memory>
 #include <vector>
 
-#include "../../include/raven_hip.h"
+#include "abi.h"
 #include "chimeric.h"
-#include "engine.h"
 #include "overlap_rules.h"
 #include "wave.h"
 
@@ -464,13 +463,6 @@ std::shared_ptr<ResolveState> resolve_state_of_arrays(Engine& e, const Overlap* 
 // ---- C ABI (include/raven_hip.h) -----------------------------------------------------------------------------------
 using namespace rvn;
 
-namespace {
-int fail_inval(const char* msg) {
-  set_last_error(msg);
-  return RVN_EINVAL;
-}
-}  // namespace
-
 // The per-pile result on the host (a snapshot of the call that made it); the lists stay in HBM with the state.
 struct rvn_resolved {
   Engine* e = nullptr;
@@ -525,21 +517,21 @@ std::unique_ptr<rvn_resolved> snapshot(Engine& e, const std::shared_ptr<ResolveS
 
 int rvn_pass1_resolve(rvn_pass1* p, const rvn_reads* rr, uint32_t coverage, double identity, uint32_t phases,
                       rvn_resolved** out) {
-  return engine_guarded(p ? p->e : nullptr, [&]() -> int {
-    if (!p || !out) return fail_inval("[raven_hip] rvn_pass1_resolve: NULL argument");
+  return guarded(p ? p->e : nullptr, [&]() -> int {
+    if (!p || !out) return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: NULL argument");
     *out = nullptr;
-    if (phases == 0 || phases > 3) return fail_inval("[raven_hip] rvn_pass1_resolve: phases must be 1, 2 or 3");
-    if (coverage > 65535) return fail_inval("[raven_hip] coverage threshold above 65535");
+    if (phases == 0 || phases > 3) return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: phases must be 1, 2 or 3");
+    if (coverage > 65535) return fail(RVN_EINVAL, "[raven_hip] coverage threshold above 65535");
     if (identity != 0 && (phases & 1u)) {
-      if (!rr) return fail_inval("[raven_hip] rvn_pass1_resolve: the identity filter needs the reads");
+      if (!rr) return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: the identity filter needs the reads");
       if (rr->r.n != p->ps.n || !rr->r.ids_are_indices)
-        return fail_inval("[raven_hip] rvn_pass1_resolve: the reads are not the ones of this pass (ids[i] == i)");
+        return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: the reads are not the ones of this pass (ids[i] == i)");
     }
     PileState& ps = p->ps;
     if (ps.resolve && (ps.resolve->phases_done & phases))
-      return fail_inval("[raven_hip] rvn_pass1_resolve: this phase has already run on this pass");
+      return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: this phase has already run on this pass");
     if (ps.resolve && (phases & 1u))
-      return fail_inval("[raven_hip] rvn_pass1_resolve: ResolveContainedReads cannot follow ResolveChimericSequences");
+      return fail(RVN_EINVAL, "[raven_hip] rvn_pass1_resolve: ResolveContainedReads cannot follow ResolveChimericSequences");
     Engine& e = *p->e;
     RVN_HIP(hipSetDevice(e.device));
     UseTimers ut(e);
@@ -548,7 +540,7 @@ int rvn_pass1_resolve(rvn_pass1* p, const rvn_reads* rr, uint32_t coverage, doub
     try {
       run_phases(e, *ps.resolve, rr ? &rr->r : nullptr, identity, phases);
     } catch (const DeviceOutOfMemory& ex) {
-      // engine_guarded repeats a call that ran out of device memory.  A state made by this call is made again; one that
+      // guarded() repeats a call that ran out of device memory.  A state made by this call is made again; one that
       // an earlier call left holds that call's result and is kept (phase 2 allocates before it changes anything).
       if (fresh) {
         ps.resolve.reset();
@@ -566,11 +558,10 @@ int rvn_resolve_contained_and_chimeric(rvn_engine* h, const rvn_reads* rr, const
                                        const uint32_t* regions, const uint32_t* region_offsets, const uint32_t* begin,
                                        const uint32_t* end, const uint16_t* median, const uint8_t* invalid, double identity,
                                        uint32_t phases, rvn_resolved** out) {
-  return engine_guarded(h ? &h->e : nullptr, [&]() -> int {
+  return guarded(h ? &h->e : nullptr, [&]() -> int {
     const char* who = "[raven_hip] rvn_resolve_contained_and_chimeric: ";
     auto bad = [&](const char* what) {
-      set_last_error(std::string(who) + what);
-      return RVN_EINVAL;
+      return fail(RVN_EINVAL, std::string(who) + what);
     };
     if (!h || !out || !offsets || !coverage_offsets || !region_offsets ||
         (n_piles && (!begin || !end || !median || !invalid)) || (offsets[n_piles] && !overlaps) ||
@@ -614,7 +605,7 @@ uint64_t rvn_resolved_coverage_words(const rvn_resolved* r) { return r && r->st-
 int rvn_resolved_fetch(const rvn_resolved* r, uint32_t* begin, uint32_t* end, uint8_t* invalid, uint8_t* contained,
                        uint8_t* chimeric, uint32_t* regions, uint32_t* region_offsets, uint16_t* median, rvn_overlap* overlaps,
                        uint32_t* offsets, uint16_t* coverage, rvn_resolve_stats* stats) {
-  if (!r) return fail_inval("[raven_hip] NULL resolved result");
+  if (!r) return fail(RVN_EINVAL, "[raven_hip] NULL resolved result");
   const u32 n = r->n;
   if (begin && n) std::memcpy(begin, r->begin.data(), n * 4ULL);
   if (end && n) std::memcpy(end, r->end.data(), n * 4ULL);
@@ -629,11 +620,11 @@ int rvn_resolved_fetch(const rvn_resolved* r, uint32_t* begin, uint32_t* end, ui
     std::memcpy(stats, &r->stats, sizeof(ResolveStats));
   }
   if (!overlaps && !offsets && !coverage) return RVN_OK;
-  if (r->engine_life.expired()) return fail_inval("[raven_hip] the engine of this result is gone");
-  return engine_guarded(r->e, [&]() -> int {
+  if (r->engine_life.expired()) return fail(RVN_EINVAL, "[raven_hip] the engine of this result is gone");
+  return guarded(r->e, [&]() -> int {
     const ResolveState& st = *r->st;
     if ((overlaps || offsets) && st.phases_done != r->phases_done)
-      return fail_inval("[raven_hip] rvn_resolved_fetch: a later phase on the same pass has consumed these lists");
+      return fail(RVN_EINVAL, "[raven_hip] rvn_resolved_fetch: a later phase on the same pass has consumed these lists");
     RVN_HIP(hipSetDevice(r->e->device));
     if (overlaps && st.n_overlaps)
       RVN_HIP(hipMemcpy(overlaps, st.ovl.ptr, st.n_overlaps * sizeof(Overlap), hipMemcpyDeviceToHost));

@@ -27,45 +27,160 @@ ED_PAIR_DTYPE = np.dtype([
 
 RVN_OK, RVN_EINVAL, RVN_ENODEVICE, RVN_EHIP, RVN_ENOMEM = 0, -1, -2, -3, -4
 
-# every symbol include/raven_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "rvn_group_create", "rvn_group_destroy", "rvn_group_size", "rvn_group_engine",
-    "rvn_group_find_overlaps_and_create_piles", "rvn_group_polish_round",
-    "rvn_last_error", "rvn_device_count", "rvn_engine_create", "rvn_engine_destroy", "rvn_reads_upload",
-    "rvn_reads_destroy", "rvn_engine_minimize", "rvn_engine_filter", "rvn_engine_occurrence",
-    "rvn_engine_map_batch", "rvn_engine_map_fetch", "rvn_engine_map_fetch_filtered",
-    "rvn_find_overlaps_and_create_piles", "rvn_pass1_pile_words", "rvn_pass1_num_overlaps",
-    "rvn_pass1_fetch_piles", "rvn_pass1_fetch_overlaps", "rvn_pass1_destroy", "rvn_pile_add_layers",
-    "rvn_edit_distance_batch", "rvn_poa_consensus_batch", "rvn_pass1_trim_and_annotate", "rvn_poa_phase_cycles", "rvn_poa_narrow_windows", "rvn_polish_target_reads", "rvn_polish_set_chunk_windows", "rvn_polish_round_range", "rvn_polish_map_best", "rvn_polish_set_best", "rvn_shard_sketch", "rvn_shard_sketch_fetch",
-    "rvn_shard_index_build", "rvn_shard_key_counts", "rvn_engine_set_occurrence", "rvn_shard_join",
-    "rvn_shard_join_fetch", "rvn_shard_chain", "rvn_shard_piles", "rvn_shard_join_range", "rvn_shard_piles_create",
-    "rvn_shard_piles_merge", "rvn_shard_piles_merge_dev", "rvn_shard_sketch_fetch_dev",
-    "rvn_shard_index_build_dev", "rvn_shard_key_histogram", "rvn_shard_join_fetch_dev", "rvn_shard_chain_dev",
-    "rvn_shard_split_minimizers_dev", "rvn_shard_count_flagged_dev", "rvn_shard_adjacent_diff_dev", "rvn_shard_regroup_dev",
-    "rvn_shard_split_overlaps_dev", "rvn_shard_piles_merge_parts_dev",
-    "rvn_engine_map_fetch_dev", "rvn_shard_piles_dev", "rvn_poa_set_mode", "rvn_poa_fallback_windows", "rvn_poa_wide_windows", "rvn_pile_add_kmers_batch",
-    "rvn_reads_attach_quality", "rvn_polish_fetch_layers", "rvn_poa_work", "rvn_reads_upload_codes", "rvn_polish_round",
-    "rvn_engine_sketch", "rvn_engine_sketch_fetch", "rvn_engine_index_size", "rvn_engine_index_fetch",
-    "rvn_engine_counters", "rvn_engine_num_stages", "rvn_engine_stage_name", "rvn_engine_stage_ms",
-    "rvn_engine_reset_stats", "rvn_engine_set_timing", "rvn_engine_set_kernel_timing",
-    "rvn_engine_num_kernel_sites", "rvn_engine_kernel_site_name", "rvn_engine_kernel_ms",
-    "rvn_engine_map_collect", "rvn_free",
-    "rvn_find_overlaps_and_repetitive_regions", "rvn_pass2_num_overlaps", "rvn_pass2_kmer_cells", "rvn_pass2_fetch",
-    "rvn_pass2_destroy", "rvn_engine_release_scratch", "rvn_filter_overlaps_by_identity", "rvn_pass1_find_chimeric_regions",
-    "rvn_reads_load", "rvn_reads_name", "rvn_reads_info", "rvn_reads_fetch", "rvn_engine_set_option", "rvn_overlap_update_and_type", "rvn_group_polish_round_q", "rvn_group_peer_access", "rvn_shard_sketch_range", "rvn_group_find_overlaps_and_create_piles_batched",
-    "rvn_polish_output_as_reads", "rvn_group_find_overlaps_and_repetitive_regions", "rvn_group_filter_overlaps_by_identity",
-    "rvn_resolve_repeat_induced_overlaps", "rvn_repeats_num_overlaps", "rvn_repeats_num_regions", "rvn_repeats_fetch",
-    "rvn_repeats_destroy",
-    "rvn_pass1_resolve", "rvn_resolve_contained_and_chimeric", "rvn_resolved_num_overlaps", "rvn_resolved_num_regions",
-    "rvn_resolved_coverage_words", "rvn_resolved_fetch", "rvn_resolved_destroy",
-]
+# The C ABI as ctypes sees it: name -> (restype, argtypes), one entry per symbol of include/raven_hip.h (tests/test_abi.py
+# compares the keys with the header).  Handles and arrays are void pointers; _declare() applies the table to a loaded library.
+_vp, _u32, _u64, _i32, _i64, _dbl, _cstr = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_int64, C.c_double, C.c_char_p
+_pp, _pu32, _pu64, _pdbl = C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+_SIGNATURES = {
+    "rvn_last_error": (_cstr, []),
+    "rvn_device_count": (_i32, []),
+    "rvn_engine_create": (_i32, [_pp, _u32, _u32, _u32, _u32, _u32, _u32, _i32]),
+    "rvn_engine_destroy": (None, [_vp]),
+    "rvn_reads_upload": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u32, _pp]),
+    "rvn_reads_upload_codes": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp]),
+    "rvn_polish_output_as_reads": (_i32, [_vp, _pp]),
+    "rvn_reads_destroy": (None, [_vp]),
+    "rvn_reads_load": (_i32, [_vp, _cstr, _pp, _vp]),
+    "rvn_reads_name": (_cstr, [_vp, _u32]),
+    "rvn_reads_info": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_reads_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_reads_attach_quality": (_i32, [_vp, _vp, _vp, _vp, _i32]),
+    "rvn_engine_minimize": (_i32, [_vp, _vp, _u32, _u32, _i32]),
+    "rvn_engine_filter": (_i32, [_vp, _dbl]),
+    "rvn_engine_occurrence": (_u32, [_vp]),
+    "rvn_engine_map_batch": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32, _i32, _i32, _pu64]),
+    "rvn_engine_map_fetch": (_i32, [_vp, _vp, _vp]),
+    "rvn_engine_map_fetch_filtered": (_i32, [_vp, _vp, _vp, _pu64]),
+    "rvn_engine_map_collect": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32, _i32, _i32, _pp, _pp, _pp, _pp]),
+    "rvn_free": (None, [_vp]),
+    "rvn_engine_release_scratch": (_i32, [_vp]),
+    "rvn_find_overlaps_and_create_piles": (_i32, [_vp, _vp, _dbl, _u32, _i32, _u64, _u64, _pp]),
+    "rvn_pass1_pile_words": (_u64, [_vp]),
+    "rvn_pass1_num_overlaps": (_u64, [_vp]),
+    "rvn_pass1_fetch_piles": (_i32, [_vp, _vp, _vp]),
+    "rvn_pass1_trim_and_annotate": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp]),
+    "rvn_pass1_find_chimeric_regions": (_i32, [_vp, _vp, _vp, _pp]),
+    "rvn_pass1_fetch_overlaps": (_i32, [_vp, _vp, _vp]),
+    "rvn_pass1_destroy": (None, [_vp]),
+    "rvn_find_overlaps_and_repetitive_regions": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _u32, _dbl, _u64, _pp]),
+    "rvn_pass2_num_overlaps": (_u64, [_vp]),
+    "rvn_pass2_kmer_cells": (_u64, [_vp]),
+    "rvn_pass2_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "rvn_pass2_destroy": (None, [_vp]),
+    "rvn_resolve_repeat_induced_overlaps": (_i32, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "rvn_repeats_num_overlaps": (_u64, [_vp]),
+    "rvn_repeats_num_regions": (_u64, [_vp]),
+    "rvn_repeats_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_repeats_destroy": (None, [_vp]),
+    "rvn_pass1_resolve": (_i32, [_vp, _vp, _u32, _dbl, _u32, _pp]),
+    "rvn_resolve_contained_and_chimeric": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _dbl, _u32, _pp]),
+    "rvn_resolved_num_overlaps": (_u64, [_vp]),
+    "rvn_resolved_num_regions": (_u64, [_vp]),
+    "rvn_resolved_coverage_words": (_u64, [_vp]),
+    "rvn_resolved_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_resolved_destroy": (None, [_vp]),
+    "rvn_filter_overlaps_by_identity": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl]),
+    "rvn_pile_add_layers": (_i32, [_vp, _vp, _u32, _u32, _vp, _u64]),
+    "rvn_pile_add_kmers_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "rvn_edit_distance_batch": (_i32, [_vp, _vp, _vp, _u32, _vp, _pdbl, _pu64]),
+    "rvn_poa_consensus_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp,
+                                       _vp, _vp, _vp, _pdbl]),
+    "rvn_polish_round": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                _vp, _vp]),
+    "rvn_shard_sketch": (_i32, [_vp, _vp, _i32, _pu64]),
+    "rvn_shard_sketch_range": (_i32, [_vp, _vp, _u32, _u32, _i32, _i32, _vp]),
+    "rvn_shard_sketch_fetch": (_i32, [_vp, _vp, _vp]),
+    "rvn_shard_index_build": (_i32, [_vp, _vp, _vp, _u64, _i32]),
+    "rvn_shard_key_counts": (_i32, [_vp, _vp]),
+    "rvn_engine_set_occurrence": (_i32, [_vp, _u32]),
+    "rvn_shard_join": (_i32, [_vp, _u32, _i32, _i32, _pu64]),
+    "rvn_shard_join_range": (_i32, [_vp, _u32, _i32, _i32, _u32, _u32, _pu64]),
+    "rvn_shard_join_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "rvn_shard_chain": (_i32, [_vp, _vp, _vp, _vp, _vp, _pu64]),
+    "rvn_shard_piles": (_i32, [_vp, _vp, _u32, _vp, _u64, _u32, _pp]),
+    "rvn_shard_piles_create": (_i32, [_vp, _vp, _u32, _pp]),
+    "rvn_shard_piles_merge": (_i32, [_vp, _vp, _u64, _u32]),
+    "rvn_shard_piles_merge_dev": (_i32, [_vp, _vp, _vp, _u64, _u32]),
+    "rvn_shard_sketch_fetch_dev": (_i32, [_vp, _vp, _vp]),
+    "rvn_shard_index_build_dev": (_i32, [_vp, _vp, _vp, _u64, _i32, _u64]),
+    "rvn_shard_key_histogram": (_i32, [_vp, _vp, _vp, _u32, _pu32]),
+    "rvn_shard_join_fetch_dev": (_i32, [_vp, _vp, _vp, _vp]),
+    "rvn_shard_chain_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _pu64]),
+    "rvn_engine_map_fetch_dev": (_i32, [_vp, _vp, _vp]),
+    "rvn_shard_split_minimizers_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp]),
+    "rvn_shard_count_flagged_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "rvn_shard_adjacent_diff_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "rvn_shard_regroup_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "rvn_shard_split_overlaps_dev": (_i32, [_vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp]),
+    "rvn_shard_piles_merge_parts_dev": (_i32, [_vp, _u32, _vp, _vp, _u32]),
+    "rvn_shard_piles_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _u64, _u32, _pp]),
+    "rvn_polish_map_best": (_i32, [_vp, _vp, _vp, _u32, _u32, _dbl, _vp, _vp, _vp]),
+    "rvn_polish_set_best": (_i32, [_vp, _vp, _vp, _u32]),
+    "rvn_polish_round_range": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _u32, _i32, _i32, _i32, _i32, _u64, _u64,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_group_create": (_i32, [_pp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u32]),
+    "rvn_group_destroy": (None, [_vp]),
+    "rvn_group_size": (_u32, [_vp]),
+    "rvn_group_engine": (_vp, [_vp, _u32]),
+    "rvn_group_find_overlaps_and_create_piles": (_i32, [_vp, _vp, _vp, _vp, _u32, _dbl, _u32, _i32, _u64, _vp, _pp]),
+    "rvn_group_find_overlaps_and_create_piles_batched": (_i32, [_vp, _vp, _vp, _vp, _u32, _dbl, _u32, _i32, _u64,
+                                                                _u64, _vp, _pp]),
+    "rvn_group_polish_round": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _dbl, _dbl, _u32, _i32, _i32,
+                                      _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rvn_group_polish_round_q": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _i32, _dbl, _dbl,
+                                        _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rvn_group_peer_access": (_i32, [_vp, _vp]),
+    "rvn_group_find_overlaps_and_repetitive_regions": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _dbl, _u32,
+                                                              _dbl, _u64, _pp]),
+    "rvn_group_filter_overlaps_by_identity": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _dbl]),
+    "rvn_overlap_update_and_type": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
+    "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
+    "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
+    "rvn_polish_target_reads": (_i32, [_vp, _vp, _u32]),
+    "rvn_poa_phase_cycles": (None, [_vp, _vp]),
+    "rvn_poa_work": (None, [_vp, _vp]),
+    "rvn_poa_set_mode": (_i32, [_vp, _i32]),
+    "rvn_poa_fallback_windows": (_u32, [_vp]),
+    "rvn_poa_wide_windows": (_u32, [_vp]),
+    "rvn_poa_narrow_windows": (_u32, [_vp]),
+    "rvn_engine_sketch": (_i32, [_vp, _vp, _u32, _u32, _i32, _pu64]),
+    "rvn_engine_sketch_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "rvn_engine_index_size": (_i32, [_vp, _pu64, _pu64]),
+    "rvn_engine_index_fetch": (_i32, [_vp, _vp, _vp]),
+    "rvn_engine_counters": (_i32, [_vp, _vp]),
+    "rvn_engine_num_stages": (_i32, []),
+    "rvn_engine_stage_name": (_cstr, [_i32]),
+    "rvn_engine_stage_ms": (_i32, [_vp, _vp, _vp, _i32]),
+    "rvn_engine_reset_stats": (None, [_vp]),
+    "rvn_engine_set_timing": (None, [_vp, _i32]),
+    "rvn_engine_set_kernel_timing": (None, [_vp, _i32]),
+    "rvn_engine_num_kernel_sites": (_i32, []),
+    "rvn_engine_kernel_site_name": (_cstr, [_i32]),
+    "rvn_engine_kernel_ms": (_i32, [_vp, _vp, _vp, _i32]),
+}
+SYMBOLS = list(_SIGNATURES)
 
 # TEST INFRASTRUCTURE: what include/raven_hip_test.h declares on top (libraven_hip_test.so only)
-TEST_SYMBOLS = [
-    "rvn_poa_banded_emulate", "rvn_test_low_complexity", "rvn_test_nw_breakpoints", "rvn_test_hash",
-    "rvn_test_canonical", "rvn_test_std_sort_lendesc", "rvn_test_heap_sort_lendesc", "rvn_test_overlap_update_and_type", "rvn_test_find_chimeric_regions",
-    "rvn_test_parse_file", "rvn_test_freelist", "rvn_test_inflate_fast", "rvn_test_ed_lane",
-]
+_TEST_SIGNATURES = {
+    "rvn_poa_banded_emulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                      _vp, _i32]),
+    "rvn_test_hash": (_u64, [_u64, _u32, _i32]),
+    "rvn_test_canonical": (_i32, [_vp, _u32, _u32, _i32, _pu64, _pu32]),
+    "rvn_test_low_complexity": (_i32, [_vp, _u32]),
+    "rvn_test_nw_breakpoints": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _i32, _u32, _u32, _i32, _vp,
+                                       _vp, _vp]),
+    "rvn_test_find_chimeric_regions": (_i64, [_vp, _u32, _vp, _u64]),
+    "rvn_test_overlap_update_and_type": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "rvn_test_parse_file": (_i32, [_cstr, _i32, _u32, _i32, _u64, _pp, _pp, _pp, _pu32, _pp, _vp]),
+    "rvn_test_inflate_fast": (_i32, [_vp, _u64, _vp, _u64, _u64, _vp]),
+    "rvn_test_freelist": (_i32, [_u64, _u64, _vp, _u32, _vp, _vp]),
+    "rvn_test_ed_lane": (_i32, [_vp, _vp, _vp, _u32, _vp, _i32, _vp]),
+    "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
+    "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
+}
+TEST_SYMBOLS = list(_TEST_SIGNATURES)
 
 
 class RavenHipError(RuntimeError):
@@ -103,141 +218,16 @@ def test_lib():
         raise RavenHipError("libraven_hip_test.so not built (%s): run raven_amd/csrc/build.sh" % TEST_LIB_PATH)
     L = C.CDLL(TEST_LIB_PATH)
     _declare(L)
-    vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-    L.rvn_test_low_complexity.restype = i32
-    L.rvn_test_low_complexity.argtypes = [vp, u32]
-    L.rvn_test_nw_breakpoints.argtypes = [vp, u32, vp, u32, u32, u32, u32, u32, i32, u32, u32, i32, vp, vp, vp]
-    L.rvn_test_nw_breakpoints.restype = i32
-    L.rvn_test_find_chimeric_regions.argtypes = [vp, u32, vp, u64]
-    L.rvn_test_find_chimeric_regions.restype = C.c_int64
-    L.rvn_test_overlap_update_and_type.argtypes = [vp, u64, vp, vp, vp, u32, vp, vp]
-    L.rvn_poa_banded_emulate.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, i32, i32, i32, i32, vp, vp, vp, vp, i32]
-    L.rvn_test_hash.restype = u64
-    L.rvn_test_hash.argtypes = [u64, u32, i32]
-    L.rvn_test_canonical.restype = i32
-    L.rvn_test_canonical.argtypes = [vp, u32, u32, i32, C.POINTER(u64), C.POINTER(u32)]
-    L.rvn_test_std_sort_lendesc.argtypes = [vp, u64]
-    L.rvn_test_heap_sort_lendesc.argtypes = [vp, u64]
-    pp = C.POINTER(C.c_void_p)
-    L.rvn_test_parse_file.argtypes = [C.c_char_p, i32, u32, i32, u64, pp, pp, pp, C.POINTER(u32), pp, vp]
-    L.rvn_test_freelist.argtypes = [u64, u64, vp, u32, vp, vp]
-    L.rvn_test_inflate_fast.argtypes = [vp, u64, vp, u64, u64, vp]
-    L.rvn_test_ed_lane.argtypes = [vp, vp, vp, u32, vp, i32, vp]
-    L.rvn_test_ed_lane.restype = i32
+    _declare(L, _TEST_SIGNATURES)
     _test_lib = L
     return L
 
 
-def _declare(L):
-    vp, u32, u64, i32, dbl = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double
-    pp = C.POINTER(C.c_void_p)
-    L.rvn_last_error.restype = C.c_char_p
-    L.rvn_device_count.restype = i32
-    L.rvn_engine_create.argtypes = [pp, u32, u32, u32, u32, u32, u32, i32]
-    L.rvn_engine_destroy.argtypes = [vp]
-    L.rvn_reads_upload.argtypes = [vp, vp, u64, vp, vp, vp, u32, pp]
-    L.rvn_reads_destroy.argtypes = [vp]
-    L.rvn_engine_minimize.argtypes = [vp, vp, u32, u32, i32]
-    L.rvn_engine_filter.argtypes = [vp, dbl]
-    L.rvn_engine_occurrence.restype = u32
-    L.rvn_engine_occurrence.argtypes = [vp]
-    L.rvn_engine_map_batch.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, C.POINTER(u64)]
-    L.rvn_engine_map_fetch.argtypes = [vp, vp, vp]
-    L.rvn_engine_map_fetch_filtered.argtypes = [vp, vp, vp, C.POINTER(u64)]
-    L.rvn_engine_map_collect.argtypes = [vp, vp, u32, u32, i32, i32, i32, i32, pp, pp, pp, pp]
-    L.rvn_free.argtypes = [vp]
-    L.rvn_find_overlaps_and_create_piles.argtypes = [vp, vp, dbl, u32, i32, u64, u64, pp]
-    L.rvn_pass1_pile_words.restype = u64
-    L.rvn_pass1_pile_words.argtypes = [vp]
-    L.rvn_pass1_num_overlaps.restype = u64
-    L.rvn_pass1_num_overlaps.argtypes = [vp]
-    L.rvn_pass1_fetch_piles.argtypes = [vp, vp, vp]
-    L.rvn_pass1_fetch_overlaps.argtypes = [vp, vp, vp]
-    L.rvn_pass1_destroy.argtypes = [vp]
-    L.rvn_pile_add_layers.argtypes = [vp, vp, u32, u32, vp, u64]
-    L.rvn_pile_add_kmers_batch.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
-    L.rvn_reads_attach_quality.argtypes = [vp, vp, vp, vp, i32]
-    L.rvn_reads_upload_codes.argtypes = [vp, vp, vp, vp, u32, pp]
-    L.rvn_polish_output_as_reads.argtypes = [vp, pp]
-    L.rvn_find_overlaps_and_repetitive_regions.argtypes = [vp, vp, vp, vp, vp, dbl, u32, dbl, u64, pp]
-    L.rvn_pass2_num_overlaps.argtypes = [vp]
-    L.rvn_pass2_num_overlaps.restype = u64
-    L.rvn_pass2_kmer_cells.argtypes = [vp]
-    L.rvn_pass2_kmer_cells.restype = u64
-    L.rvn_pass2_fetch.argtypes = [vp, vp, vp, vp, vp]
-    L.rvn_pass2_destroy.argtypes = [vp]
-    L.rvn_engine_release_scratch.argtypes = [vp]
-    L.rvn_filter_overlaps_by_identity.argtypes = [vp, vp, vp, vp, vp, vp, vp, dbl]
-    L.rvn_group_create.argtypes = [pp, u32, u32, u32, u32, u32, u32, vp, u32]
-    L.rvn_group_destroy.argtypes = [vp]
-    L.rvn_group_destroy.restype = None
-    L.rvn_group_size.argtypes = [vp]
-    L.rvn_group_size.restype = u32
-    L.rvn_group_engine.argtypes = [vp, u32]
-    L.rvn_group_engine.restype = vp
-    L.rvn_group_find_overlaps_and_repetitive_regions.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, dbl, u32, dbl, u64, pp]
-    L.rvn_group_filter_overlaps_by_identity.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, dbl]
-    L.rvn_reads_load.argtypes = [vp, C.c_char_p, pp, vp]
-    L.rvn_reads_name.argtypes = [vp, u32]
-    L.rvn_reads_name.restype = C.c_char_p
-    L.rvn_reads_info.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.rvn_reads_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.rvn_pass1_find_chimeric_regions.argtypes = [vp, vp, vp, pp]
-    L.rvn_poa_work.argtypes = [vp, vp]
-    L.rvn_poa_work.restype = None
-    L.rvn_polish_fetch_layers.argtypes = [vp, vp, u64, C.POINTER(u64)]
-    L.rvn_polish_round.argtypes = [vp, vp, vp, vp, vp, dbl, dbl, u32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.rvn_edit_distance_batch.argtypes = [vp, vp, vp, u32, vp, C.POINTER(dbl), C.POINTER(u64)]
-    L.rvn_poa_consensus_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, i32, i32, i32, vp, vp, vp, vp,
-                                          C.POINTER(dbl)]
-    L.rvn_poa_phase_cycles.argtypes = [vp, vp]
-    L.rvn_polish_target_reads.argtypes = [vp, vp, u32]
-    L.rvn_polish_set_chunk_windows.argtypes = [vp, u64]
-    L.rvn_polish_set_chunk_windows.restype = u64
-    L.rvn_shard_sketch.argtypes = [vp, vp, i32, C.POINTER(u64)]
-    L.rvn_shard_sketch_fetch.argtypes = [vp, vp, vp]
-    L.rvn_shard_index_build.argtypes = [vp, vp, vp, u64, i32]
-    L.rvn_shard_key_counts.argtypes = [vp, vp]
-    L.rvn_engine_set_occurrence.argtypes = [vp, u32]
-    L.rvn_shard_join.argtypes = [vp, u32, i32, i32, C.POINTER(u64)]
-    L.rvn_shard_join_fetch.argtypes = [vp, vp, vp, vp]
-    L.rvn_shard_join_range.argtypes = [vp, u32, i32, i32, u32, u32, C.POINTER(u64)]
-    L.rvn_shard_piles_create.argtypes = [vp, vp, u32, C.POINTER(vp)]
-    L.rvn_shard_piles_merge.argtypes = [vp, vp, u64, u32]
-    L.rvn_shard_piles_merge_dev.argtypes = [vp, vp, vp, u64, u32]
-    L.rvn_shard_chain.argtypes = [vp, vp, vp, vp, vp, C.POINTER(u64)]
-    L.rvn_shard_piles.argtypes = [vp, vp, u32, vp, u64, u32, C.POINTER(vp)]
-    L.rvn_shard_sketch_fetch_dev.argtypes = [vp, vp, vp]
-    L.rvn_shard_index_build_dev.argtypes = [vp, vp, vp, u64, i32, u64]
-    L.rvn_shard_key_histogram.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
-    L.rvn_shard_join_fetch_dev.argtypes = [vp, vp, vp, vp]
-    L.rvn_shard_chain_dev.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
-    L.rvn_engine_map_fetch_dev.argtypes = [vp, vp, vp]
-    L.rvn_shard_piles_dev.argtypes = [vp, vp, u32, vp, vp, u64, u32, C.POINTER(vp)]
-    L.rvn_poa_set_mode.argtypes = [vp, i32]
-    L.rvn_poa_set_mode.restype = i32
-    L.rvn_poa_fallback_windows.argtypes = [vp]
-    L.rvn_poa_fallback_windows.restype = u32
-    L.rvn_poa_wide_windows.argtypes = [vp]
-    L.rvn_poa_wide_windows.restype = u32
-    L.rvn_poa_narrow_windows.argtypes = [vp]
-    L.rvn_poa_narrow_windows.restype = u32
-    L.rvn_engine_sketch.argtypes = [vp, vp, u32, u32, i32, C.POINTER(u64)]
-    L.rvn_engine_sketch_fetch.argtypes = [vp, vp, vp, vp]
-    L.rvn_engine_index_size.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-    L.rvn_engine_index_fetch.argtypes = [vp, vp, vp]
-    L.rvn_engine_counters.argtypes = [vp, vp]
-    L.rvn_engine_num_stages.restype = i32
-    L.rvn_engine_stage_name.restype = C.c_char_p
-    L.rvn_engine_stage_name.argtypes = [i32]
-    L.rvn_engine_stage_ms.argtypes = [vp, vp, vp, i32]
-    L.rvn_engine_reset_stats.argtypes = [vp]
-    L.rvn_engine_set_timing.argtypes = [vp, i32]
-    L.rvn_engine_set_kernel_timing.argtypes = [vp, i32]
-    L.rvn_engine_num_kernel_sites.restype = i32
-    L.rvn_engine_kernel_site_name.restype = C.c_char_p
-    L.rvn_engine_kernel_site_name.argtypes = [i32]
-    L.rvn_engine_kernel_ms.argtypes = [vp, vp, vp, i32]
+def _declare(L, signatures=_SIGNATURES):
+    for name, (restype, argtypes) in signatures.items():
+        f = getattr(L, name)
+        f.restype = restype
+        f.argtypes = argtypes
 
 
 def _p(a):
@@ -340,12 +330,6 @@ def _fetch_resolved(h, n):
     """rvn_resolved_fetch of everything, then rvn_resolved_destroy: the dict Pass1.resolve and
     Engine.resolve_contained_and_chimeric return."""
     L = lib()
-    vp, u64 = C.c_void_p, C.c_uint64
-    for f in (L.rvn_resolved_num_overlaps, L.rvn_resolved_num_regions, L.rvn_resolved_coverage_words):
-        f.argtypes = [vp]
-        f.restype = u64
-    L.rvn_resolved_fetch.argtypes = [vp] * 13
-    L.rvn_resolved_destroy.argtypes = [vp]
     try:
         begin, end = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         invalid, contained, chimeric = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
@@ -382,7 +366,6 @@ class Pass1:
         it stays on the pass, see piles()), stats)."""
         L = lib()
         h = C.c_void_p()
-        L.rvn_pass1_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_void_p)]
         _check(L.rvn_pass1_resolve(self._h, reads._h if reads is not None else None, int(coverage), float(identity),
                                    int(phases), C.byref(h)))
         return _fetch_resolved(h, self.n)
@@ -406,7 +389,6 @@ class Pass1:
         ptrs = (C.c_void_p * max(n, 1))(*[int(a) for a, _ in parts])
         cnts = (C.c_uint64 * max(n, 1))(*[int(c) for _, c in parts])
         L = lib()
-        L.rvn_shard_piles_merge_parts_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         _check(L.rvn_shard_piles_merge_parts_dev(self._h, n, ptrs, cnts, kmax))
 
     def merge_dev(self, d_overlaps, d_read_off, n, kmax=32):
@@ -415,7 +397,6 @@ class Pass1:
     def trim_and_annotate(self, coverage=4):
         """Pile::FindValidRegion(coverage) + FindMedian for every pile, in place in HBM: (begin, end, median, invalid)."""
         L = lib()
-        L.rvn_pass1_trim_and_annotate.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
         b = np.zeros(self.n, dtype=np.uint32)
         e = np.zeros(self.n, dtype=np.uint32)
         m = np.zeros(self.n, dtype=np.uint16)
@@ -717,21 +698,17 @@ class Engine:
     def shard_split_minimizers_dev(self, d_val, d_org, n, world, d_val_out, d_org_out):
         counts = (C.c_uint64 * world)()
         L = lib()
-        L.rvn_shard_split_minimizers_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p]
         _check(L.rvn_shard_split_minimizers_dev(self._h, d_val, d_org, int(n), world, d_val_out, d_org_out, counts))
         return [int(x) for x in counts]
 
     def shard_count_flagged_dev(self, d_org, n) -> int:
         c = C.c_uint64(0)
         L = lib()
-        L.rvn_shard_count_flagged_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _check(L.rvn_shard_count_flagged_dev(self._h, d_org, int(n), C.byref(c)))
         return int(c.value)
 
     def shard_adjacent_diff_dev(self, d_seg, n, d_cnt):
         L = lib()
-        L.rvn_shard_adjacent_diff_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _check(L.rvn_shard_adjacent_diff_dev(self._h, d_seg, int(n), d_cnt))
 
     def shard_regroup_dev(self, d_cnt, d_grp, d_pos, n_src, n_reads, d_seg, d_grp_out, d_pos_out):
@@ -739,8 +716,6 @@ class Engine:
         arr = lambda xs: (C.c_void_p * world)(*[int(x) for x in xs])
         ns = (C.c_uint64 * world)(*[int(x) for x in n_src])
         L = lib()
-        L.rvn_shard_regroup_dev.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         _check(L.rvn_shard_regroup_dev(self._h, world, arr(d_cnt), arr(d_grp), arr(d_pos), ns, int(n_reads), d_seg,
                                        d_grp_out, d_pos_out))
 
@@ -748,8 +723,6 @@ class Engine:
         b = np.ascontiguousarray(bounds, dtype=np.uint32)
         counts = (C.c_uint64 * (world + 1))()
         L = lib()
-        L.rvn_shard_split_overlaps_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                   C.c_void_p, C.c_void_p]
         _check(L.rvn_shard_split_overlaps_dev(self._h, d_ovl, int(n), _p(b), world, self_rank, d_out, counts))
         return [int(x) for x in counts]
 
@@ -796,9 +769,6 @@ class Engine:
             np.cumsum([len(x) for x in quals], out=qo[1:])
             qa = np.concatenate([np.asarray(x, dtype=np.uint8) for x in quals])
         L = lib()
-        L.rvn_polish_round_range.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                             C.c_double, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                             C.c_uint64, C.c_uint64] + [C.c_void_p] * 7
         _check(L.rvn_polish_round_range(self._h, targets._h, reads._h, _p(qa), _p(qo), float(q), float(err), w,
                                         int(trim), m, n, g, int(window_first), int(window_last), _p(out), _p(ooff),
                                         _p(out_len), None, _p(nw), _p(npol), _p(stats)))
@@ -818,8 +788,6 @@ class Engine:
         bt = np.zeros(max(n, 1), dtype=np.uint32)
         n_ovl = C.c_uint64(0)
         L = lib()
-        L.rvn_polish_map_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
         _check(L.rvn_polish_map_best(self._h, targets._h, reads._h, int(read_first), read_last, float(err), _p(best),
                                      _p(bt), C.byref(n_ovl)))
         return best[:n], bt[:n], int(n_ovl.value)
@@ -831,7 +799,6 @@ class Engine:
         bt = np.ascontiguousarray(best_target, dtype=np.uint32)
         assert best.shape[0] == bt.shape[0]
         L = lib()
-        L.rvn_polish_set_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         _check(L.rvn_polish_set_best(self._h, _p(best), _p(bt), int(bt.shape[0])))
 
     # -- second mapping pass and identity filter (construct.cc:316-491, :162-217) ------------------------------------
@@ -880,14 +847,6 @@ class Engine:
         assert en.shape[0] == n and med.shape[0] == n and inv.shape[0] == n and coff.shape[0] == n + 1 == koff.shape[0]
         h = C.c_void_p()
         L = lib()
-        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-        L.rvn_resolve_repeat_induced_overlaps.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)]
-        L.rvn_repeats_num_overlaps.argtypes = [vp]
-        L.rvn_repeats_num_overlaps.restype = u64
-        L.rvn_repeats_num_regions.argtypes = [vp]
-        L.rvn_repeats_num_regions.restype = u64
-        L.rvn_repeats_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.rvn_repeats_destroy.argtypes = [vp]
         _check(L.rvn_resolve_repeat_induced_overlaps(self._h, _p(o), o.shape[0], n, _p(cov), _p(coff), _p(km), _p(koff),
                                                      _p(b), _p(en), _p(med), _p(inv), C.byref(h)))
         try:
@@ -923,9 +882,6 @@ class Engine:
         assert o.shape[0] == int(off[-1]) and cov.shape[0] == int(coff[-1]) and reg.shape[0] == 2 * int(roff[-1])
         h = C.c_void_p()
         L = lib()
-        vp = C.c_void_p
-        L.rvn_resolve_contained_and_chimeric.argtypes = [vp, vp, vp, vp, C.c_uint32] + [vp] * 8 + [C.c_double, C.c_uint32,
-                                                                                                C.POINTER(vp)]
         _check(L.rvn_resolve_contained_and_chimeric(self._h, reads._h if reads is not None else None, _p(o), _p(off), n,
                                                     _p(cov), _p(coff), _p(reg), _p(roff), _p(b), _p(en), _p(med), _p(inv),
                                                     float(identity), int(phases), C.byref(h)))
@@ -1041,7 +997,6 @@ class Engine:
         reproducible per value of that option, not across values); returns the previous value.  Unknown names raise."""
         prev = C.c_int64(0)
         L = lib()
-        L.rvn_engine_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]
         _check(L.rvn_engine_set_option(self._h, name.encode(), int(value), C.byref(prev)))
         return int(prev.value)
 

@@ -22,9 +22,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "raven_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-UNITS = ["scan", "radix_sort", "sketch", "index", "map", "pile", "edit_distance", "poa", "poa2", "poa4", "polish", "nwpath",
-         "pass2", "io", "shard", "group", "engine", "edlib_dropin", "simt_emu"]
 INSTRUMENTED = ["poa4", "poa", "simt_emu"]
+
+
+def _units():
+    """The translation units of the test library, from the one place that names them (csrc/build.sh)."""
+    out = subprocess.run(["bash", os.path.join(CSRC, "build.sh"), "--print-units"], capture_output=True, text=True, check=True).stdout
+    lists = dict(line.split(":", 1) for line in out.splitlines())
+    return lists["product"].split() + lists["test_only"].split()
 
 SCRIPT = r"""
 import numpy as np
@@ -60,7 +65,9 @@ def test_window_consensus_kernel_source_under_address_and_ub_sanitizers(tmp_path
     rt = _asan_runtime()
     if rt is None:
         pytest.skip("this ROCm has no shared AddressSanitizer runtime")
-    others = [os.path.join(CSRC, "obj_test", u + ".o") for u in UNITS if u not in INSTRUMENTED]
+    units = _units()
+    assert set(INSTRUMENTED) <= set(units)
+    others = [os.path.join(CSRC, "obj_test", u + ".o") for u in units if u not in INSTRUMENTED]
     if not all(os.path.exists(o) for o in others):
         pytest.skip("the test library's objects are not in the tree (raven_amd/csrc/build.sh leaves them in obj_test/)")
     flags = ["--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-Wno-unused-function", "-DRVN_TEST_HOOKS", "-DRVN_DEBUG_KNOBS",
@@ -71,10 +78,16 @@ def test_window_consensus_kernel_source_under_address_and_ub_sanitizers(tmp_path
         _, err = j.communicate(timeout=1500)
         assert j.returncode == 0, (u, err[-2000:])
     lib = str(tmp_path / "libraven_hip_test.so")
-    objs = [str(tmp_path / (u + ".o")) if u in INSTRUMENTED else os.path.join(CSRC, "obj_test", u + ".o") for u in UNITS]
+    objs = [str(tmp_path / (u + ".o")) if u in INSTRUMENTED else os.path.join(CSRC, "obj_test", u + ".o") for u in units]
     link = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-shared-libsan",
                            "-o", lib] + objs + ["-lz"], capture_output=True, text=True, timeout=900)
     assert link.returncode == 0, link.stderr[-2000:]
+    # the list of units is complete: the instrumented library exports what the product and the test library export
+    from raven_amd import hip
+    nm = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if line.strip()}
+    missing = sorted(set(hip.SYMBOLS + hip.TEST_SYMBOLS) - exported)
+    assert not missing, missing
     env = dict(os.environ, RVN_LIB_PATH=lib, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", PYTHONPATH=ROOT)
     run = subprocess.run([sys.executable, "-c", SCRIPT], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert run.returncode == 0 and "AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, (run.stdout[-1000:], run.stderr[-3000:])

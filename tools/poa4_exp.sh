@@ -14,7 +14,7 @@ case $1 in
     wait
     for n in $VARIANTS; do
       objs=""
-      for f in $C/obj_test/*.o; do [ "$(basename $f)" = "poa4.o" ] || objs="$objs $f"; done
+      for u in $(bash $C/build.sh --print-units | cut -d: -f2); do [ "$u" = "poa4" ] || objs="$objs $C/obj_test/$u.o"; done
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o $R/raven_amd/lib_exp/libraven_hip_test_$n.so $objs $C/obj_exp/poa4_$n.o -lz
     done
     ls -la $R/raven_amd/lib_exp/;;
