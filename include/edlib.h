@@ -5,7 +5,9 @@
  *     RavenLib/src/construct.cc:407-416   identity filter of the second pass
  *     (also RavenLib/src/assemble.cc:271-277, RavenLib/src/graph_repr.cc:250,361, RavenTest/src/raven_test.cpp:39-44)
  * all of which are  edlibAlign(q, qlen, t, tlen, edlibDefaultAlignConfig())  ->  result.status / result.editDistance
- * ->  edlibFreeAlignResult(result).
+ * ->  edlibFreeAlignResult(result);  and racon's  edlibAlign(q, qlen, t, tlen, edlibNewAlignConfig(-1, EDLIB_MODE_NW,
+ * EDLIB_TASK_PATH, nullptr, 0))  ->  edlibAlignmentToCigar(result.alignment, result.alignmentLength, ...)  of
+ * Overlap::find_breaking_points (behind RavenLib/src/polish.cc:43-51).
  *
  * What runs where: the distance is computed on the GPU by the batched Myers kernel behind rvn_edit_distance_batch
  * (raven_hip.h).  edlibAlign is a blocking single-pair call, and Raven issues it from many pool threads at once
@@ -13,11 +15,21 @@
  * queue inside the library), so N threads cost one upload + one launch, not N.  A hot loop that owns all its pairs
  * up front should call rvn_edit_distance_batch on spans of the uploaded reads instead (no inflate, no upload).
  *
- * Supported: EDLIB_MODE_NW with EDLIB_TASK_DISTANCE (edlibDefaultAlignConfig), any k (k < 0 = unbounded; a distance
- * above k >= 0 is reported as -1 exactly as edlib does), sequences over at most 4 distinct symbols (the device
+ * Supported: EDLIB_MODE_NW with every task, any k (k < 0 = unbounded; a distance above k >= 0 is reported as -1
+ * exactly as edlib does, without locations or alignment), sequences over at most 4 distinct symbols (the device
  * works on 2-bit codes; equality of bytes is what is compared, like edlib without additional equalities).
- * Anything else — SHW / HW modes, LOC / PATH tasks, additional equalities, more than 4 distinct symbols, no usable
- * GPU — returns status EDLIB_STATUS_ERROR; there is no CPU path in this library. */
+ *   EDLIB_TASK_DISTANCE  editDistance, endLocations = { targetLength - 1 }
+ *   EDLIB_TASK_LOC       the same plus startLocations = { 0 }
+ *   EDLIB_TASK_PATH      the same plus alignment / alignmentLength: one EDLIB_EDOP_* byte per column of an optimal
+ *                        alignment (rvn_align_path_batch, raven_hip.h).  Among the optimal alignments the one taken
+ *                        prefers, walking back from the end, the diagonal, then 'I' (query base only), then 'D'
+ *                        (target base only); edlib itself documents no tie rule, so the op string of an ambiguous pair
+ *                        may differ from edlib's while its cost is the same.
+ * Requests of all three tasks that are in flight at the same time share the combining queue.  A hot loop that owns all
+ * its pairs up front should call rvn_align_path_batch on spans of the uploaded reads instead.
+ * Anything else — SHW / HW modes, additional equalities, more than 4 distinct symbols, a PATH request whose band is
+ * beyond the alignment stage's limits, no usable GPU — returns status EDLIB_STATUS_ERROR; there is no CPU path in this
+ * library. */
 #ifndef EDLIB_H
 #define EDLIB_H
 
@@ -45,7 +57,7 @@ typedef struct {
 typedef struct {
   int k;                /* >= 0: report -1 when the distance is larger; < 0: unbounded */
   EdlibAlignMode mode;  /* only EDLIB_MODE_NW */
-  EdlibAlignTask task;  /* only EDLIB_TASK_DISTANCE */
+  EdlibAlignTask task;  /* DISTANCE, LOC or PATH */
   const EdlibEqualityPair* additionalEqualities; /* must be NULL */
   int additionalEqualitiesLength;                /* must be 0 */
 } EdlibAlignConfig;
@@ -59,9 +71,9 @@ typedef struct {
   int status;          /* EDLIB_STATUS_OK / EDLIB_STATUS_ERROR */
   int editDistance;    /* -1 when larger than k */
   int* endLocations;   /* NW: { targetLength - 1 }; NULL when editDistance == -1; freed by edlibFreeAlignResult */
-  int* startLocations; /* NULL (distance task) */
+  int* startLocations; /* LOC / PATH: { 0 }; NULL for the distance task */
   int numLocations;
-  unsigned char* alignment; /* NULL (distance task) */
+  unsigned char* alignment; /* PATH: alignmentLength EDLIB_EDOP_* bytes, malloc'ed, freed by edlibFreeAlignResult; else NULL */
   int alignmentLength;
   int alphabetLength; /* distinct symbols in query and target */
 } EdlibAlignResult;
@@ -72,7 +84,7 @@ void edlibFreeAlignResult(EdlibAlignResult result);
 EdlibAlignResult edlibAlign(const char* query, int queryLength, const char* target, int targetLength,
                             const EdlibAlignConfig config);
 
-/* edlib's CIGAR printer (host string formatting only; provided so that code using it links).  Returns a malloc'ed,
+/* edlib's CIGAR printer (host string formatting of a PATH result's alignment).  Returns a malloc'ed,
  * zero-terminated string the caller frees, or NULL. */
 char* edlibAlignmentToCigar(const unsigned char* alignment, int alignmentLength, EdlibCigarFormat cigarFormat);
 

@@ -308,6 +308,45 @@ typedef struct rvn_ed_pair {
 int rvn_edit_distance_batch(rvn_engine* e, const rvn_reads* r, const rvn_ed_pair* pairs, uint32_t n_pairs,
                             uint32_t* distances, double* device_ms, uint64_t* cells);
 
+/* Batched global alignment PATHS of read spans: what racon gets from edlibAlign(query, target, EDLIB_MODE_NW,
+ * EDLIB_TASK_PATH) in Overlap::find_breaking_points, behind racon::Polisher::Initialize / Polish of
+ * RavenLib/src/polish.cc:43-51 — the alignment-path stage of rvn_polish_round, with the path itself as the result.
+ * Pair i aligns a span of read `query_read` of `queries` with a span of read `target_read` of `targets` (the two sets may
+ * be one handle); begins are counted in the reads as stored, and strand == 0 reverse-complements the query span first.
+ * The path is an optimal one (its cost is the exact edit distance).  Where several are optimal the walk, which goes from
+ * the end of the alignment to its start, prefers the diagonal ('=' or 'X'), then a query base only ('I'), then a target
+ * base only ('D').  edlib documents NO tie rule for the paths it returns — any optimal path is "the" edlib path —, so the
+ * distance, not the op string, is what agrees with edlib on every input.
+ * Result (a handle; its arrays stay on the device until they are fetched):
+ *   distances[n_pairs]     the exact edit distance; 0xFFFFFFFF: not aligned (below)
+ *   run_offsets[n_pairs+1] the runs of pair i are runs[run_offsets[i] .. run_offsets[i + 1])
+ *   runs[n_runs]           count << 2 | op, op = EDLIB_EDOP_* (0 '=', 1 'I', 2 'D', 3 'X'), in alignment order from the
+ *                          start; adjacent runs of a pair have different ops.  'I' consumes a query base, 'D' a target
+ *                          base: counts of ops {0, 3, 1} add up to query_len, of {0, 3, 2} to target_len, and the ops
+ *                          other than '=' to distances[i].  An empty query gives one 'D' run, an empty target one 'I'
+ *                          run, both empty no run.
+ *   ops (rvn_paths_fetch_ops)  the same paths as edlib's alignment array, one byte per op, expanded on the device;
+ *                          pair i at ops[op_offsets[i] .. op_offsets[i + 1]), n_ops bytes in all
+ * A pair whose band is beyond the stage's limits (the ones that make a polishing round count n_dropped_layers: a band of
+ * more than eight rings of eight 64-row blocks per lane, or one whose stored columns exceed the engine option
+ * nw_budget_mb) gets distance 0xFFFFFFFF and no runs and is counted in n_not_aligned; that is not an error of the call.
+ * A read index outside its set or a span outside its read: RVN_EINVAL.
+ * The alignment of (lhs, reverse complement of rhs) of a Raven overlap: pass rhs as the QUERY with strand = 0, lhs as the
+ * target, and swap 'I' and 'D' in the result. */
+typedef struct rvn_align_pair {
+  uint32_t query_read, query_begin, query_len;    /* span of read `query_read` of `queries`, as stored */
+  uint32_t target_read, target_begin, target_len; /* span of read `target_read` of `targets` */
+  uint32_t strand;   /* 0: the query span is reverse-complemented before it is aligned; 1: as stored */
+  uint32_t reserved;
+} rvn_align_pair;
+typedef struct rvn_paths rvn_paths;
+int rvn_align_path_batch(rvn_engine* e, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                         uint32_t n_pairs, rvn_paths** out);
+int rvn_paths_info(const rvn_paths* p, uint32_t* n_pairs, uint64_t* n_runs, uint64_t* n_ops, uint32_t* n_not_aligned);
+int rvn_paths_fetch(const rvn_paths* p, uint32_t* distances, uint64_t* run_offsets, uint32_t* runs);
+int rvn_paths_fetch_ops(const rvn_paths* p, uint64_t* op_offsets, uint8_t* ops);
+void rvn_paths_destroy(rvn_paths* p);
+
 /* Batched racon Window::GenerateConsensus (the POA consensus behind racon::Polisher::Polish,
  * RavenLib/src/polish.cc:43-51; scores = AlignCfg of polish.hpp:13-17): for every window, layer 0 is the
  * backbone, the others are the read pieces aligned to it.

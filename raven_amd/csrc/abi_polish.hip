@@ -1,11 +1,19 @@
-// abi_polish.hip — C ABI (include/raven_hip.h): polishing rounds and the window-consensus batch.
+// abi_polish.hip — C ABI (include/raven_hip.h): polishing rounds, the window-consensus batch and the alignment paths of
+// the polishing front end as a batch call of their own.
 #include <algorithm>
 #include <cstring>
 
 #include "abi.h"
+#include "nwpath.h"
 #include "poa.h"
 
 using namespace rvn;
+
+struct rvn_paths {
+  rvn::Engine* e = nullptr;
+  std::weak_ptr<int> engine_life;  // a handle may outlive its engine
+  rvn::NwPaths p;
+};
 
 extern "C" {
 
@@ -123,6 +131,88 @@ int rvn_polish_round(rvn_engine* h, rvn_reads* targets, rvn_reads* reads, const 
   return rvn_polish_round_range(h, targets, reads, read_quals, qual_offsets, q, err, w, trim, match, mismatch, gap, 0,
                                 ~0ULL, out_codes, out_offsets, out_len, ratio, nullptr, nullptr, stats);
 }
+
+int rvn_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                         uint32_t n_pairs, rvn_paths** out) {
+  return guarded(h, h && queries && targets && out && (pairs || !n_pairs), "[raven_hip] rvn_align_path_batch: NULL argument",
+                 [&](Engine& e) -> int {
+    static_assert(sizeof(rvn_align_pair) == 32, "pair layout");
+    const ReadsDev& Q = queries->r;
+    const ReadsDev& T = targets->r;
+    std::vector<NwJob> jobs(n_pairs);
+    for (uint32_t i = 0; i < n_pairs; ++i) {
+      const rvn_align_pair& p = pairs[i];
+      if (p.query_read >= Q.n || p.target_read >= T.n)
+        return fail(RVN_EINVAL, "[raven_hip] rvn_align_path_batch: read index outside its set");
+      const u32 qlen = Q.h_len[p.query_read];
+      if (static_cast<u64>(p.query_begin) + p.query_len > qlen ||
+          static_cast<u64>(p.target_begin) + p.target_len > T.h_len[p.target_read])
+        return fail(RVN_EINVAL, "[raven_hip] rvn_align_path_batch: span outside its read");
+      const bool rc = p.strand == 0;
+      NwJob& J = jobs[i];
+      J = NwJob{};
+      J.t_word = T.h_word_off[p.target_read];
+      J.r_word = Q.h_word_off[p.query_read];
+      J.t_begin = p.target_begin;
+      J.n = p.target_len;
+      J.q_begin = rc ? qlen - p.query_begin - p.query_len : p.query_begin;  // (in the orientation it is aligned in)
+      J.m = p.query_len;
+      J.r_len = qlen;
+      J.rc = rc ? 1 : 0;
+      J.read = p.query_read;
+      J.target = p.target_read;
+      J.n_windows = 1;
+    }
+    std::unique_ptr<rvn_paths> res(new rvn_paths());
+    res->e = &e;
+    res->engine_life = e.life;
+    nw_align_paths(e, T, Q, jobs, res->p);
+    *out = res.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_paths_info(const rvn_paths* p, uint32_t* n_pairs, uint64_t* n_runs, uint64_t* n_ops, uint32_t* n_not_aligned) {
+  if (!p) return fail(RVN_EINVAL, "[raven_hip] rvn_paths_info: NULL handle");
+  if (n_pairs) *n_pairs = p->p.n;
+  if (n_runs) *n_runs = p->p.n_runs;
+  if (n_ops) *n_ops = p->p.n_ops;
+  if (n_not_aligned) *n_not_aligned = p->p.n_not_aligned;
+  return RVN_OK;
+}
+
+int rvn_paths_fetch(const rvn_paths* p, uint32_t* distances, uint64_t* run_offsets, uint32_t* runs) {
+  if (!p || p->engine_life.expired()) return fail(RVN_EINVAL, "[raven_hip] rvn_paths_fetch: NULL handle, or its engine is gone");
+  return guarded(p->e, [&]() -> int {
+    const NwPaths& P = p->p;
+    RVN_HIP(hipSetDevice(p->e->device));
+    if (distances && P.n) std::memcpy(distances, P.distances.data(), static_cast<size_t>(P.n) * 4);
+    if (run_offsets) RVN_HIP(hipMemcpy(run_offsets, P.run_off.ptr, (static_cast<size_t>(P.n) + 1) * 8, hipMemcpyDeviceToHost));
+    if (runs && P.n_runs) RVN_HIP(hipMemcpy(runs, P.runs.ptr, static_cast<size_t>(P.n_runs) * 4, hipMemcpyDeviceToHost));
+    return RVN_OK;
+  });
+}
+
+int rvn_paths_fetch_ops(const rvn_paths* p, uint64_t* op_offsets, uint8_t* ops) {
+  if (!p || p->engine_life.expired()) return fail(RVN_EINVAL, "[raven_hip] rvn_paths_fetch_ops: NULL handle, or its engine is gone");
+  return guarded(p->e, [&]() -> int {
+    const NwPaths& P = p->p;
+    Engine& e = *p->e;
+    RVN_HIP(hipSetDevice(e.device));
+    UseTimers ut(e);
+    if (op_offsets) RVN_HIP(hipMemcpy(op_offsets, P.op_off.ptr, (static_cast<size_t>(P.n) + 1) * 8, hipMemcpyDeviceToHost));
+    if (ops && P.n_ops) {
+      DevBuf d_ops;
+      u8* d = d_ops.get<u8>(static_cast<size_t>(P.n_ops));
+      nw_paths_expand(e, P, d);
+      RVN_HIP(hipMemcpyAsync(ops, d, static_cast<size_t>(P.n_ops), hipMemcpyDeviceToHost, e.stream));
+      RVN_HIP(rvn_stream_sync(e.stream));
+    }
+    return RVN_OK;
+  });
+}
+
+void rvn_paths_destroy(rvn_paths* p) { delete p; }
 
 uint64_t rvn_polish_set_chunk_windows(rvn_engine* h, uint64_t windows) {
   if (!h) return 0;

@@ -1,5 +1,6 @@
-// edlib_dropin.hip — the edlib C entry points Raven's overlap path calls (include/edlib.h), on top of the batched
-// device edit distance (rvn_edit_distance_batch).  Host code only: packing, a combining queue, result structs.
+// edlib_dropin.hip — the edlib C entry points Raven's overlap path and racon's alignment step call (include/edlib.h), on
+// top of the batched device edit distance (rvn_edit_distance_batch) and the batched alignment paths (rvn_align_path_batch).
+// Host code only: packing, a combining queue, result structs.
 //
 // edlibAlign is a blocking single-pair call that the reference issues from many pool threads at once
 // (RavenLib/src/construct.cc:167-212, :374-429).  One launch per pair would be all latency, so concurrent calls are
@@ -22,6 +23,8 @@ struct Request {
   std::vector<uint64_t> q_words, t_words;
   uint32_t q_len = 0, t_len = 0;
   uint32_t distance = 0;
+  bool want_path = false;      // EDLIB_TASK_PATH: the alignment too
+  std::vector<uint8_t> ops;    // ... one byte per op
   int rc = RVN_OK;
   bool done = false;
 };
@@ -58,7 +61,10 @@ struct Service {
       // one read set: query of request i = read 2i, target = read 2i+1
       std::vector<uint64_t> packed, woff(1, 0);
       std::vector<uint32_t> lens;
-      std::vector<rvn_ed_pair> pairs(batch.size());
+      // distance requests go through rvn_edit_distance_batch, path requests through rvn_align_path_batch
+      std::vector<rvn_ed_pair> pairs;
+      std::vector<rvn_align_pair> ppairs;
+      std::vector<size_t> pair_req, ppair_req;
       for (size_t i = 0; i < batch.size(); ++i) {
         Request* r = batch[i];
         packed.insert(packed.end(), r->q_words.begin(), r->q_words.end());
@@ -67,20 +73,50 @@ struct Service {
         packed.insert(packed.end(), r->t_words.begin(), r->t_words.end());
         woff.push_back(packed.size());
         lens.push_back(r->t_len);
-        pairs[i] = rvn_ed_pair{static_cast<uint32_t>(2 * i), 0, r->q_len, static_cast<uint32_t>(2 * i + 1), 0, r->t_len, 1, 0};
+        if (r->want_path) {
+          ppairs.push_back(rvn_align_pair{static_cast<uint32_t>(2 * i), 0, r->q_len, static_cast<uint32_t>(2 * i + 1), 0, r->t_len, 1, 0});
+          ppair_req.push_back(i);
+        } else {
+          pairs.push_back(rvn_ed_pair{static_cast<uint32_t>(2 * i), 0, r->q_len, static_cast<uint32_t>(2 * i + 1), 0, r->t_len, 1, 0});
+          pair_req.push_back(i);
+        }
       }
       packed.push_back(0);
       rvn_reads* reads = nullptr;
       rc = rvn_reads_upload(engine, packed.data(), packed.size() - 1, woff.data(), lens.data(), nullptr,
                             static_cast<uint32_t>(lens.size()), &reads);
-      if (rc == RVN_OK) {
-        std::vector<uint32_t> dist(batch.size());
+      if (rc == RVN_OK && !pairs.empty()) {
+        std::vector<uint32_t> dist(pairs.size());
         rc = rvn_edit_distance_batch(engine, reads, pairs.data(), static_cast<uint32_t>(pairs.size()), dist.data(),
                                      nullptr, nullptr);
         if (rc == RVN_OK)
-          for (size_t i = 0; i < batch.size(); ++i) batch[i]->distance = dist[i];
+          for (size_t i = 0; i < pairs.size(); ++i) batch[pair_req[i]]->distance = dist[i];
+      }
+      std::vector<int> rc_of(batch.size(), RVN_OK);
+      if (rc == RVN_OK && !ppairs.empty()) {
+        rvn_paths* paths = nullptr;
+        rc = rvn_align_path_batch(engine, reads, reads, ppairs.data(), static_cast<uint32_t>(ppairs.size()), &paths);
+        uint64_t n_ops = 0;
+        if (rc == RVN_OK) rc = rvn_paths_info(paths, nullptr, nullptr, &n_ops, nullptr);
+        std::vector<uint32_t> dist(ppairs.size());
+        std::vector<uint64_t> off(ppairs.size() + 1);
+        std::vector<uint8_t> ops(n_ops + 1);
+        if (rc == RVN_OK) rc = rvn_paths_fetch(paths, dist.data(), nullptr, nullptr);
+        if (rc == RVN_OK) rc = rvn_paths_fetch_ops(paths, off.data(), ops.data());
+        if (rc == RVN_OK)
+          for (size_t i = 0; i < ppairs.size(); ++i) {
+            Request* r = batch[ppair_req[i]];
+            r->distance = dist[i];
+            if (dist[i] == 0xFFFFFFFFu) rc_of[ppair_req[i]] = RVN_EHIP;  // beyond the stage's limits: this request alone fails
+            else r->ops.assign(ops.begin() + off[i], ops.begin() + off[i + 1]);
+          }
+        rvn_paths_destroy(paths);
       }
       rvn_reads_destroy(reads);
+      if (rc == RVN_OK) {
+        for (size_t i = 0; i < batch.size(); ++i) batch[i]->rc = rc_of[i];
+        return;
+      }
     }
     for (Request* r : batch) r->rc = rc;
   }
@@ -174,9 +210,11 @@ void edlibFreeAlignResult(EdlibAlignResult result) {
 EdlibAlignResult edlibAlign(const char* query, int queryLength, const char* target, int targetLength,
                             const EdlibAlignConfig config) {
   if (queryLength < 0 || targetLength < 0 || (queryLength && !query) || (targetLength && !target)) return error_result();
-  if (config.mode != EDLIB_MODE_NW || config.task != EDLIB_TASK_DISTANCE || config.additionalEqualitiesLength != 0)
-    return error_result();  // only the configuration Raven's hot path uses runs on the device; no CPU path here
+  if (config.mode != EDLIB_MODE_NW || config.additionalEqualitiesLength != 0)
+    return error_result();  // global alignment over plain byte equality runs on the device; no CPU path here
+  if (config.task != EDLIB_TASK_DISTANCE && config.task != EDLIB_TASK_LOC && config.task != EDLIB_TASK_PATH) return error_result();
   Request req;
+  req.want_path = config.task == EDLIB_TASK_PATH;
   int code_of[256];
   for (int& c : code_of) c = -1;
   int n_symbols = 0;
@@ -200,6 +238,22 @@ EdlibAlignResult edlibAlign(const char* query, int queryLength, const char* targ
   if (!r.endLocations) return error_result();
   r.endLocations[0] = targetLength - 1;
   r.numLocations = 1;
+  if (config.task == EDLIB_TASK_DISTANCE) return r;
+  r.startLocations = static_cast<int*>(std::malloc(sizeof(int)));  // a global alignment starts at the target's first base
+  if (!r.startLocations) {
+    edlibFreeAlignResult(r);
+    return error_result();
+  }
+  r.startLocations[0] = 0;
+  if (config.task == EDLIB_TASK_PATH) {
+    r.alignmentLength = static_cast<int>(req.ops.size());
+    r.alignment = static_cast<unsigned char*>(std::malloc(req.ops.size() + 1));
+    if (!r.alignment) {
+      edlibFreeAlignResult(r);
+      return error_result();
+    }
+    if (!req.ops.empty()) std::memcpy(r.alignment, req.ops.data(), req.ops.size());
+  }
   return r;
 }
 

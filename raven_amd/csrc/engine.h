@@ -349,9 +349,26 @@ struct NwStats {
   u64 band_cells = 0, sum_distance = 0, store_bytes = 0;
   double ms = 0;
 };
+// the path form's slots (nwpath.hip): the blocks the walks wrote their runs into, per job where its runs end
+struct NwPathSlots {
+  std::vector<std::unique_ptr<DevBuf>> blocks;
+  std::vector<u64> slot_end;  // device address of the word behind the job's runs (it holds their number); 0: not walked
+};
 // distances (optional): per job the exact distance, ~0 for a job that was not aligned
 void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& R, std::vector<NwJob>& jobs, u32 w, NwWindowRec* d_recs,
-                    u64 n_recs, NwStats& st, std::vector<u32>* distances = nullptr);
+                    u64 n_recs, NwStats& st, std::vector<u32>* distances = nullptr, NwPathSlots* path = nullptr);
+// The alignment paths of a batch of pairs (rvn_align_path_batch): jobs as polishing builds them (rows = target span,
+// columns = query span in the target's orientation; empty spans allowed), results on the device in pair order.
+struct NwPaths {
+  u32 n = 0, n_not_aligned = 0;
+  u64 n_runs = 0, n_ops = 0;
+  std::vector<u32> distances;      // exact edit distance; ~0: not aligned
+  DevBuf run_off, runs, op_off;    // u64[n + 1], u32[n_runs] (count << 2 | op, alignment order), u64[n + 1]
+  double device_ms = 0;
+};
+void nw_align_paths(Engine& e, const ReadsDev& T, const ReadsDev& Q, std::vector<NwJob>& jobs, NwPaths& out);
+// runs -> one byte per op (edlib's alignment array) into d_ops[n_ops]
+void nw_paths_expand(Engine& e, const NwPaths& p, u8* d_ops);
 // the same code stepped on the CPU (64 emulated lanes): test hook, see rvn_test_nw_breakpoints
 int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r_len, u32 t_begin, u32 n, u32 q_begin, u32 m,
                         int rc, u32 w, u32 k, int force_R, NwWindowRec* recs, u32* distance, u32* band);

@@ -24,8 +24,10 @@
 //             optimal path is "the" edlib path.  Banded values equal the full-matrix values on every cell the walk can
 //             take (each lies on an optimal alignment, which the band contains); values the band only bounds from above
 //             (entering blocks, the +1 boundary of retired ones) can never pass a test the true value fails, so the path
-//             is the full-matrix path.  The walk emits no CIGAR: it folds find_breaking_points in and writes, per
-//             window, the first / last aligned pair and the read offsets at eight fixed target positions (POA band guide).
+//             is the full-matrix path.  For polishing the walk emits no CIGAR: it folds find_breaking_points in and writes,
+//             per window, the first / last aligned pair and the read offsets at eight fixed target positions (POA band guide).
+//             A walker with an op SINK (NwRunSink below) also says what it did: one (op, count) per step or run, merged into
+//             maximal runs — the path form of the stage (nw_align_paths, rvn_align_path_batch).
 #pragma once
 
 #include "myers.h"
@@ -273,11 +275,74 @@ __host__ __device__ __forceinline__ BlockPlanes nw_load_planes(const u64* __rest
   return p;
 }
 
+// ---- op sinks of the walker ------------------------------------------------------------------------------------------
+// The walker tells its sink every step or run it takes, op = edlib's EDLIB_EDOP_*: 0 a run of equal bases ('='), 3 a
+// substitution ('X'), 1 a read (query) base only ('I'), 2 a target base only ('D').  The sink is a compile-time property of
+// the walker: polishing walks with NwNoSink, whose calls are empty.
+constexpr u32 kNwOpMatch = 0, kNwOpInsert = 1, kNwOpDelete = 2, kNwOpMismatch = 3;
+
+struct NwNoSink {
+  static constexpr bool kOn = false;
+  __host__ __device__ void put(u32, u32, bool) {}
+  __host__ __device__ bool close(bool) { return true; }
+};
+
+// A path of distance d has at most 2 d + 1 maximal runs (d ops that are not '=', at most d + 1 match runs between and
+// around them), and a job is only walked when d <= its threshold k: a slot of 2 k + 1 words always holds it, and the host
+// knows k when it queues the job — no counting pass, no look at the distance.  One more word behind the slot takes the
+// number of runs.
+__host__ __device__ inline u64 nw_slot_words(u32 k) { return 2ULL * k + 2; }
+
+// Keeps the current run in registers; when the op changes it writes one word, count << 2 | op.  Consecutive events of one
+// op merge — also the match runs the walker cuts at strip, block and window ends.  The walk goes from the end of the
+// alignment to its start, so the slot is filled from the back: afterwards the runs stand in alignment order in
+// end[-count .. 0) and end[0] = count.  write: this lane stores (the group walk: lane 0; every lane counts alike).
+struct NwRunSink {
+  static constexpr bool kOn = true;
+  u32* lo;   // first word of the slot
+  u32* end;  // one past its last run word
+  u32* p;    // the last word written
+  u32 op, cnt;
+  bool full;
+  __host__ __device__ void init(u32* slot, u64 words) {
+    lo = slot;
+    end = slot + (words - 1);
+    p = end;
+    op = cnt = 0;
+    full = false;
+  }
+  __host__ __device__ void emit(bool write) {
+    if (cnt == 0) return;
+    if (p == lo) {  // (more runs than the bound: an inconsistent walk — never past the slot)
+      full = true;
+      return;
+    }
+    --p;
+    if (write) *p = (cnt << 2) | op;
+  }
+  __host__ __device__ void put(u32 o, u32 c, bool write) {
+    if (o == op) {
+      cnt += c;
+      return;
+    }
+    emit(write);
+    op = o;
+    cnt = c;
+  }
+  __host__ __device__ bool close(bool write) {
+    emit(write);
+    cnt = 0;
+    if (write) *end = static_cast<u32>(end - p);
+    return !full;
+  }
+};
+
 // The backward walk, resumable strip by strip.  Cells answers, for a mismatching cell (i, j) of the strip it holds (rows
 // above row_lo, columns above seg_j0), whether the diagonal / the left neighbour is one below D(i, j).
-template <class Cells>
+template <class Cells, class Sink = NwNoSink>
 struct NwWalkerT {
   Cells cells;
+  Sink sink;
   // job
   u32 t_begin, q_begin, w, win0;
   NwWindowRec* recs;
@@ -299,7 +364,7 @@ struct NwWalkerT {
     q_begin = J.q_begin;
     w = w_;
     win0 = J.t_begin / w_;
-    recs = recs_all + J.bp_off;
+    recs = Sink::kOn && !recs_all ? nullptr : recs_all + J.bp_off;  // (a walker with a sink may walk for the sink alone)
     seg_j0 = 0;
     row_lo = 0;
     i = static_cast<int>(J.n);
@@ -317,6 +382,7 @@ struct NwWalkerT {
 
   __host__ __device__ void flush(bool write) {
     if (cw == 0xFFFFFFFFu || !write) return;
+    if (Sink::kOn && !recs) return;
     NwWindowRec e;
     e.first_t = have ? first_t : 0xFFFFFFFFu;
     e.first_q = first_q;
@@ -415,6 +481,7 @@ struct NwWalkerT {
           // the whole run inside the current window and above the next grid position: only the first pair moves
           first_t = t_lo;
           first_q = q_begin + static_cast<u32>(j - r);
+          sink.put(kNwOpMatch, static_cast<u32>(r), write);
           i -= r;
           j -= r;
           continue;
@@ -423,14 +490,18 @@ struct NwWalkerT {
         const bool same = cw != 0xFFFFFFFFu && t_hi >= cw_lo && t_hi - cw_lo < w;
         const u32 in_window = same ? t_hi - cw_lo + 1 : t_hi - (t_hi / w) * w + 1;
         r = static_cast<u32>(r) < in_window ? r : static_cast<int>(in_window);
+        sink.put(kNwOpMatch, static_cast<u32>(r), write);
         take_diag_run(r, write);
       } else if (const int mv = cells.decide(i, j); mv == 0) {  // substitution: the diagonal
         --cur;
+        sink.put(kNwOpMismatch, 1, write);
         take_diag(write);
       } else if (mv == 1) {  // 'I': read base only
+        sink.put(kNwOpInsert, 1, write);
         --j;
         --cur;
       } else {  // 'D': target base only
+        sink.put(kNwOpDelete, 1, write);
         on_target_base(t_begin + static_cast<u32>(i - 1), q_begin + static_cast<u32>(j), write);
         --i;
         --cur;
@@ -439,17 +510,20 @@ struct NwWalkerT {
   }
   // the rest needs no scores: only read bases (i == 0) or only target bases (j == 0) are left
   __host__ __device__ int finish(bool write) {
+    if (j > 0 && i == 0) sink.put(kNwOpInsert, static_cast<u32>(j), write);
     while (j > 0 && i == 0) {
       --j;
       --cur;
     }
+    if (i > 0 && j == 0) sink.put(kNwOpDelete, static_cast<u32>(i), write);
     while (i > 0 && j == 0) {
       on_target_base(t_begin + static_cast<u32>(i - 1), q_begin, write);
       --i;
       --cur;
     }
     flush(write);
-    return (cur == 0 && i == 0 && j == 0) ? 0 : 1;
+    const bool sink_ok = sink.close(write);
+    return (cur == 0 && i == 0 && j == 0 && sink_ok) ? 0 : 1;
   }
 };
 

@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <type_traits>
 #include <vector>
 
 #include "engine.h"
@@ -196,12 +197,14 @@ void nw_sweep_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx
 
 // STRIP_LDS: the walker's strip in LDS (33 KB per wave: four waves per CU) or in a per-wave scratch in HBM / L2
 // ([column][lane], coalesced; occupancy limited by registers only)
-template <bool STRIP_LDS, int SC>
+// Out: what the walk leaves — NwWindowRec, the window records of polishing (recs[J.bp_off ..]), or u32, the path form:
+// the walker's runs in the job's slot (out[J.bp_off ..], nw_slot_words(J.k) words, filled from the back: NwRunSink)
+template <bool STRIP_LDS, int SC, class Out = NwWindowRec>
 __global__ __launch_bounds__(64) void nw_trace_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx, u32 n_idx,
                                                       const u64* __restrict__ t_words, const u64* __restrict__ r_words,
                                                       const u32* __restrict__ hs, const NwPm* __restrict__ ck,
                                                       const u32* __restrict__ result, u32* __restrict__ status, u32 w,
-                                                      NwWindowRec* __restrict__ recs, u64* __restrict__ scratch) {
+                                                      Out* __restrict__ recs, u64* __restrict__ scratch) {
   // (SC = 16: a strip keeps sixteen columns, 17.4 KB of LDS per wave, nine waves per CU instead of four — nwtrace.h; for
   // launches of more waves than the machine holds with whole strips.  A walker pays ~15 % for the second visit of a
   // checkpoint interval, so launches that fit keep whole strips.)
@@ -218,17 +221,24 @@ __global__ __launch_bounds__(64) void nw_trace_kernel(const NwJob* __restrict__ 
   const NwGeo geo = nw_geo_job(J);
   u64* g_pv = scratch + static_cast<u64>(blockIdx.x) * (2 * kNwStripCols * 64);
   const NwStripMem<64> mem{STRIP_LDS ? s_pv : g_pv, STRIP_LDS ? s_mv : g_pv + kNwStripCols * 64, static_cast<int>(threadIdx.x)};
-  status[ji] = static_cast<u32>(nw_trace_job<64, SC>(J, geo, t_words, r_words, hs + J.hs, ck + J.ckpt, mem, result[ji], w, recs));
+  if constexpr (std::is_same<Out, u32>::value) {
+    NwRunSink sink;
+    sink.init(recs + J.bp_off, nw_slot_words(J.k));
+    status[ji] = static_cast<u32>(nw_trace_job<64, SC, NwRunSink>(J, geo, t_words, r_words, hs + J.hs, ck + J.ckpt, mem, result[ji], w,
+                                                                  nullptr, sink));
+  } else {
+    status[ji] = static_cast<u32>(nw_trace_job<64, SC>(J, geo, t_words, r_words, hs + J.hs, ck + J.ckpt, mem, result[ji], w, recs));
+  }
 }
 
 // The group walk (nwtrace.h: NwGroupWalk): GL lanes per alignment, 64 / GL alignments per wave; strips in the same LDS
 // array as nw_trace_kernel's (column = lane), the heads beside it: 36.9 KB per wave, four waves per CU.
-template <int GL>
+template <int GL, class Out = NwWindowRec>
 __global__ __launch_bounds__(64) void nw_trace_group_kernel(const NwJob* __restrict__ jobs, const u32* __restrict__ idx, u32 n_idx,
                                                             const u64* __restrict__ t_words, const u64* __restrict__ r_words,
                                                             const u32* __restrict__ hs, const NwPm* __restrict__ ck,
                                                             const u32* __restrict__ result, u32* __restrict__ status, u32 w,
-                                                            NwWindowRec* __restrict__ recs) {
+                                                            Out* __restrict__ recs) {
   constexpr int NG = 64 / GL;
   __shared__ u64 s_pv[kNwStripCols * 64];
   __shared__ u64 s_mv[kNwStripCols * 64];
@@ -241,8 +251,15 @@ __global__ __launch_bounds__(64) void nw_trace_group_kernel(const NwJob* __restr
   if (status[ji] != 0) return;
   const NwJob J = jobs[ji];
   const NwGeo geo = nw_geo_job(J);
-  NwGroupWalk<64, GL> G;
-  G.init(J, t_words, r_words, NwStripMem<64>{s_pv, s_mv, grp * GL}, s_heads + grp * GL, result[ji], w, recs);
+  constexpr bool kPath = std::is_same<Out, u32>::value;
+  NwGroupWalk<64, GL, typename std::conditional<kPath, NwRunSink, NwNoSink>::type> G;
+  if constexpr (kPath) {
+    NwRunSink sink;
+    sink.init(recs + J.bp_off, nw_slot_words(J.k));
+    G.init(J, t_words, r_words, NwStripMem<64>{s_pv, s_mv, grp * GL}, s_heads + grp * GL, result[ji], w, nullptr, sink);
+  } else {
+    G.init(J, t_words, r_words, NwStripMem<64>{s_pv, s_mv, grp * GL}, s_heads + grp * GL, result[ji], w, recs);
+  }
   int bad = 0;
   while (!G.done()) {
     G.fill(J, geo, hs + J.hs, ck + J.ckpt, t);
@@ -299,13 +316,19 @@ u32 level_of(const NwJob& J) {
 // engine's stream, the walk of chunk i on a second stream beside the sweeps of chunk i + 1 (two buffer sets): a walk is
 // one lane per alignment and latency-bound (~1 us per column), a sweep fills the VALUs — together they cost the time of
 // the sweeps plus the walk of the last, shortest jobs.
+//
+// path (the path form, nw_align_paths below): the walks leave their runs instead of window records (d_recs = nullptr,
+// n_recs = 0).  Every pass of walks gets a block of slots of its own, a job's slot there at its bp_off (nw_slot_words of its
+// threshold: known when it is queued); path->slot_end[job] = the device address of the word behind the runs of the job's
+// last walk.  Planning, thresholds, retries, chunks, stripes and the choice of the walk are the same code.
 void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vector<NwJob>& jobs, u32 w,
-                    NwWindowRec* d_recs, u64 n_recs, NwStats& st, std::vector<u32>* distances) {
+                    NwWindowRec* d_recs, u64 n_recs, NwStats& st, std::vector<u32>* distances, NwPathSlots* path) {
   st = NwStats();
   const u32 nj = static_cast<u32>(jobs.size());
   if (distances) distances->assign(nj, ~0u);
+  if (path) path->slot_end.assign(nj, 0);
   hipStream_t s = e.stream;
-  RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
+  if (n_recs) RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
   if (nj == 0) return;
   RVN_HIP(hipEventRecord(e.ev0, s));
   if (!e.nw_streams[0]) {
@@ -505,6 +528,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     // was measured at C4 and did not pay: every extra sweep launch brings its own ramp and tail, +19 ms of sweep time
     // against ~20 ms less at the end; profiles/r05_nw_timeline.csv.)
     std::vector<Chunk> chunks;
+    u64 slot_w = 0;  // (path form) words of the pass's slots
     struct Need {
       u64 hw, ce, cells;
       u32 level;
@@ -531,6 +555,10 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         if (c1 > c0 && (C.hs_w + hw) * 4 + (C.ck_e + ce) * 16 > share) break;
         J.hs = C.hs_w;
         J.ckpt = C.ck_e;
+        if (path && !sweep_only) {
+          J.bp_off = slot_w;
+          slot_w += nw_slot_words(J.k);
+        }
         C.hs_w += hw;
         C.ck_e += ce;
         st.band_cells += need[c1].cells;
@@ -580,6 +608,12 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       for (const Chunk& C : chunks) mc = std::max(mc, C.c1 - C.c0);
       d_strip = e.nw_strip.get<u64>(static_cast<size_t>((mc + 63) / 64) * 2 * kNwStripCols * 64 * 4 + 64);
     }
+    u32* d_slots = nullptr;
+    if (path && !sweep_only) {
+      path->blocks.emplace_back(new DevBuf());
+      d_slots = path->blocks.back()->get<u32>(slot_w + 16);
+      for (u32 i : order) path->slot_end[i] = reinterpret_cast<u64>(d_slots + jobs[i].bp_off + nw_slot_words(jobs[i].k) - 1);
+    }
     h_order += since(t_h);
     t_h = clk::now();
     if (dev.compact) {  // records in the order of the pass, addressed by position
@@ -614,30 +648,35 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       // one walk stream per buffer set: the walk of the longest alignments (chunk 0: few waves, tens of milliseconds of
       // latency) must not hold back the walks of the chunks behind it
       hipStream_t ts = one_stream ? s : e.nw_streams[b];
-      auto launch_walk = [&](hipStream_t wst, const u32* idx_w, u32 n_w) {
+      auto launch_walk_to = [&](auto* d_out, hipStream_t wst, const u32* idx_w, u32 n_w) {
+        using Out = typename std::remove_pointer<decltype(d_out)>::type;  // NwWindowRec: polishing; u32: the path form's slots
         if (group_walk == 2 || (group_walk != 1 && n_w <= kNwGroupWalkMaxJobs)) {
           // few alignments: a group of lanes each (nwtrace.h) — the walk of a few thousand alignments costs its longest one's
           // latency, and a group walks a column in a fraction of a lane's time
           constexpr u32 NG = 64 / kNwGroupLanes;
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_group_kernel<kNwGroupLanes><<<(n_w + NG - 1) / NG, 64, 0, wst>>>(
+          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_group_kernel<kNwGroupLanes, Out><<<(n_w + NG - 1) / NG, 64, 0, wst>>>(
                                                  dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_recs)));
+                                                 dev.status, w, d_out)));
         } else if (trace_lds && (group_walk == 3 || (group_walk != 1 && n_w > 64u * 4u * 256u))) {
           // more waves than four per CU hold: strips of sixteen kept columns, nine waves per CU (C4: the walk of the last
           // chunk's 140 000 shortest alignments, alone on the GPU, 18 -> 13 ms; align_ms 185 -> 174)
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwLaneStripCols><<<(n_w + 63) / 64, 64, 0, wst>>>(
+          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwLaneStripCols, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
                                                  dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_recs, nullptr)));
+                                                 dev.status, w, d_out, nullptr)));
         } else if (trace_lds) {
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwCkSteps><<<(n_w + 63) / 64, 64, 0, wst>>>(
+          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwCkSteps, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
                                                  dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_recs, nullptr)));
+                                                 dev.status, w, d_out, nullptr)));
         } else {
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<false, kNwCkSteps><<<(n_w + 63) / 64, 64, 0, wst>>>(
+          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<false, kNwCkSteps, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
                                                  dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_recs,
+                                                 dev.status, w, d_out,
                                                  d_strip + static_cast<size_t>(b) * ((e.nw_strip.cap / 32) & ~size_t(63)))));
         }
+      };
+      auto launch_walk = [&](hipStream_t wst, const u32* idx_w, u32 n_w) {
+        if (path) launch_walk_to(d_slots, wst, idx_w, n_w);
+        else launch_walk_to(d_recs, wst, idx_w, n_w);
       };
       // A variant's launch of few waves — the pilot's five, the several-blocks-per-lane variants of a round's longest
       // alignments (a few hundred jobs whose sweep is tens of thousands of dependent steps: 14-18 ms on 60-300 of the
@@ -988,6 +1027,140 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     std::fprintf(stderr, "[raven_hip] nw: %u jobs, %llu aligned, %llu retries, %llu chunks, %.3e band cells, %.1f MB hs + ck, %.1f ms; pilot mu %.4f a %.4f b %.3e\n", nj,
                  static_cast<unsigned long long>(st.n_aligned), static_cast<unsigned long long>(st.n_retries),
                  static_cast<unsigned long long>(st.n_batches), static_cast<double>(st.band_cells), st.store_bytes / 1048576.0, ms, mu, va, vb);
+}
+
+// ---- the path form: the walkers' runs, dense and in pair order; edlib's one byte per op ----------------------------------
+namespace {
+
+constexpr u32 kNwPathWindow = 1u << 30;  // one window for the whole span (spans are shorter): the walker's window logic idles
+
+// pairs 0 .. n (entry n: 0, so that the scan's last entry is the total): runs of the pair — what its walker counted, one
+// for a pair with an empty span (synth = its run), none for a pair that was not aligned or is empty on both sides
+__global__ __launch_bounds__(256) void nw_path_count_kernel(const u64* __restrict__ slot_end, const u32* __restrict__ synth,
+                                                            u32 n, u32* __restrict__ cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  u32 c = 0;
+  if (i < n) {
+    const u32* end = reinterpret_cast<const u32*>(slot_end[i]);
+    c = end ? *end : (synth[i] ? 1u : 0u);
+  }
+  cnt[i] = c;
+}
+
+// one wave per pair: the used tail of its slot to runs[run_off[pair] ..] (coalesced both ways), the ops its runs stand for
+// (the sum of their counts) to op_cnt[pair]; op_cnt[n] = 0
+__global__ __launch_bounds__(256) void nw_path_pack_kernel(const u64* __restrict__ slot_end, const u32* __restrict__ synth,
+                                                           const u64* __restrict__ run_off, u32 n, u32* __restrict__ runs,
+                                                           u32* __restrict__ op_cnt) {
+  const u32 pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = lane_id();
+  if (pair > n) return;
+  if (pair == n) {
+    if (lane == 0) op_cnt[n] = 0;
+    return;
+  }
+  const u64 o = run_off[pair];
+  const u32 c = static_cast<u32>(run_off[pair + 1] - o);
+  const u32* end = reinterpret_cast<const u32*>(slot_end[pair]);
+  const u32 one = synth[pair];
+  u32 sum = 0;
+  for (u32 x = static_cast<u32>(lane); x < c; x += 64) {
+    const u32 v = end ? end[static_cast<long long>(x) - static_cast<long long>(c)] : one;
+    runs[o + x] = v;
+    sum += v >> 2;
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) op_cnt[pair] = sum;
+}
+
+// one workgroup per pair: its runs in tiles of 256 — the tile's run lengths are scanned in LDS, then the 256 threads write
+// the tile's stretch of output side by side (consecutive threads, consecutive bytes), each finding its run by bisection
+__global__ __launch_bounds__(256) void nw_path_expand_kernel(const u64* __restrict__ run_off, const u32* __restrict__ runs,
+                                                             const u64* __restrict__ op_off, u8* __restrict__ ops) {
+  __shared__ u32 s_incl[256];
+  __shared__ u8 s_op[256];
+  __shared__ u32 s_w[4];
+  const u32 pair = blockIdx.x;
+  const u64 r0 = run_off[pair], r1 = run_off[pair + 1];
+  u8* out = ops + op_off[pair];
+  for (u64 base = r0; base < r1; base += 256) {
+    const u64 x = base + threadIdx.x;
+    const u32 v = x < r1 ? runs[x] : 0u;
+    u32 total = 0;
+    const u32 excl = block_exclusive_sum_256<u32>(v >> 2, s_w, &total);
+    s_incl[threadIdx.x] = excl + (v >> 2);
+    s_op[threadIdx.x] = static_cast<u8>(v & 3u);
+    __syncthreads();
+    for (u32 pos = threadIdx.x; pos < total; pos += 256) {
+      u32 lo = 0, hi = 255;  // the first run whose inclusive sum is above pos
+      while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (s_incl[mid] > pos) hi = mid;
+        else lo = mid + 1;
+      }
+      out[pos] = s_op[lo];
+    }
+    out += total;
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+void nw_align_paths(Engine& e, const ReadsDev& T, const ReadsDev& Q, std::vector<NwJob>& jobs, NwPaths& out) {
+  const u32 n = static_cast<u32>(jobs.size());
+  hipStream_t s = e.stream;
+  out.n = n;
+  out.n_not_aligned = 0;
+  out.n_runs = out.n_ops = 0;
+  NwPathSlots slots;
+  NwStats st;
+  nw_breakpoints(e, T, Q, jobs, kNwPathWindow, nullptr, 0, st, &out.distances, &slots);
+  out.device_ms = st.ms;
+  // a pair with an empty span has one run and no walk: the other span's bases, query only ('I') or target only ('D')
+  std::vector<u32> synth(static_cast<size_t>(n) + 1, 0);
+  for (u32 i = 0; i < n; ++i) {
+    const NwJob& J = jobs[i];
+    if (J.n == 0 || J.m == 0) {
+      out.distances[i] = J.n + J.m;
+      if (J.n + J.m) synth[i] = ((J.n + J.m) << 2) | (J.m ? kNwOpInsert : kNwOpDelete);
+    } else if (out.distances[i] == ~0u) {
+      ++out.n_not_aligned;
+      slots.slot_end[i] = 0;
+    }
+  }
+  slots.slot_end.push_back(0);
+  DevBuf d_end_b, d_synth_b, d_cnt_b;
+  u64* d_end = d_end_b.get<u64>(static_cast<size_t>(n) + 1);
+  u32* d_synth = d_synth_b.get<u32>(static_cast<size_t>(n) + 1);
+  u32* d_cnt = d_cnt_b.get<u32>(static_cast<size_t>(n) + 1);
+  u64* d_run_off = out.run_off.get<u64>(static_cast<size_t>(n) + 1);
+  u64* d_op_off = out.op_off.get<u64>(static_cast<size_t>(n) + 1);
+  RVN_HIP(hipEventRecord(e.ev0, s));
+  RVN_HIP(hipMemcpyAsync(d_end, slots.slot_end.data(), (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice, s));
+  RVN_HIP(hipMemcpyAsync(d_synth, synth.data(), (static_cast<size_t>(n) + 1) * 4, hipMemcpyHostToDevice, s));
+  RVN_KLAUNCH(kKNwTraceback, nw_path_count_kernel<<<n / 256 + 1, 256, 0, s>>>(d_end, d_synth, n, d_cnt));
+  exclusive_scan_u32_u64(d_cnt, d_run_off, static_cast<u64>(n) + 1, e.scan_tmp, s);
+  u64 total = 0;
+  RVN_HIP(hipMemcpyAsync(&total, d_run_off + n, 8, hipMemcpyDeviceToHost, s));
+  RVN_HIP(rvn_stream_sync(s));  // (also: `synth` and the slot addresses are pageable)
+  out.n_runs = total;
+  u32* d_runs = out.runs.get<u32>(static_cast<size_t>(total) + 1);
+  RVN_KLAUNCH(kKNwTraceback, nw_path_pack_kernel<<<n / 4 + 1, 256, 0, s>>>(d_end, d_synth, d_run_off, n, d_runs, d_cnt));
+  exclusive_scan_u32_u64(d_cnt, d_op_off, static_cast<u64>(n) + 1, e.scan_tmp, s);
+  RVN_HIP(hipMemcpyAsync(&total, d_op_off + n, 8, hipMemcpyDeviceToHost, s));
+  RVN_HIP(hipEventRecord(e.ev1, s));
+  RVN_HIP(rvn_stream_sync(s));  // (the slots go back when this returns)
+  out.n_ops = total;
+  float ms = 0;
+  RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
+  out.device_ms += ms;
+}
+
+void nw_paths_expand(Engine& e, const NwPaths& p, u8* d_ops) {
+  if (p.n == 0 || p.n_ops == 0) return;
+  RVN_KLAUNCH(kKNwTraceback, nw_path_expand_kernel<<<p.n, 256, 0, e.stream>>>(p.run_off.as<u64>(), p.runs.as<u32>(), p.op_off.as<u64>(), d_ops));
 }
 
 #ifdef RVN_TEST_HOOKS

@@ -93,18 +93,20 @@ __host__ __device__ inline u64 nw_hs_bits(const u32* __restrict__ hs, const NwGe
 // — a walker that leaves them to the left comes back for the rest of the interval, which is then at most sixteen columns —:
 // half the strip memory, i.e. twice the resident walkers per CU where the strips live in LDS, for 1.5x the Myers steps, which
 // are not what a wave of 64 diverged walkers is waiting for).
-template <int LANES, int SC = kNwCkSteps>
+// Sink: what the walker tells about its steps (nwpath.h; default: nothing, the polishing walk).
+template <int LANES, int SC = kNwCkSteps, class Sink = NwNoSink>
 __host__ __device__ inline int nw_trace_job(const NwJob& J, const NwGeo& g, const u64* __restrict__ t_words_all,
                                             const u64* __restrict__ r_words_all, const u32* __restrict__ hs,
                                             const NwPm* __restrict__ ck, const NwStripMem<LANES>& mem, u32 distance, u32 w,
-                                            NwWindowRec* __restrict__ recs_all) {
+                                            NwWindowRec* __restrict__ recs_all, const Sink& sink = Sink()) {
   const u64* tw = t_words_all + J.t_word;
   const u64* rw = r_words_all + J.r_word;
   const bool rc = J.rc != 0;
   const long long b_base = rc ? static_cast<long long>(J.r_len) - J.q_begin - J.m : static_cast<long long>(J.q_begin);
   const long long b_first = rc ? b_base + static_cast<long long>(J.m) - 1 : b_base;
-  NwWalkerT<NwStripCells<LANES>> wk;
+  NwWalkerT<NwStripCells<LANES>, Sink> wk;
   wk.cells.mem = mem;
+  wk.sink = sink;
   wk.init(J, distance, w, recs_all);
   const int R = g.R;
   while (wk.i > 0 && wk.j > 0) {
@@ -335,9 +337,9 @@ __host__ __device__ inline void nw_fill_strip(const NwJob& J, const NwGeo& g, co
 // mem.lane + t); heads: the group's GL heads; t: this lane's index in the group; Sync: makes the strips and heads written by
 // the group's lanes visible to all of them (one wave: a fence; the host stepper calls the phases lane by lane instead, see
 // nw_trace_group_host).  Returns 0 (records written by lane 0) or 1 (inconsistent), the same in every lane of the group.
-template <int LANES, int GL>
+template <int LANES, int GL, class Sink = NwNoSink>
 struct NwGroupWalk {
-  NwWalkerT<NwStripCells<LANES>> wk;
+  NwWalkerT<NwStripCells<LANES>, Sink> wk;
   NwStripMem<LANES> mem;
   NwStripHead* heads;
   const u64 *tw, *rw;
@@ -346,7 +348,8 @@ struct NwGroupWalk {
   int n_plan, cur;
 
   __host__ __device__ void init(const NwJob& J, const u64* __restrict__ t_words_all, const u64* __restrict__ r_words_all,
-                                const NwStripMem<LANES>& mem_, NwStripHead* heads_, u32 distance, u32 w, NwWindowRec* recs_all) {
+                                const NwStripMem<LANES>& mem_, NwStripHead* heads_, u32 distance, u32 w, NwWindowRec* recs_all,
+                                const Sink& sink = Sink()) {
     tw = t_words_all + J.t_word;
     rw = r_words_all + J.r_word;
     rc = J.rc != 0;
@@ -355,6 +358,7 @@ struct NwGroupWalk {
     mem = mem_;
     heads = heads_;
     wk.cells.mem = mem_;
+    wk.sink = sink;
     wk.init(J, distance, w, recs_all);
     n_plan = 0;
     cur = 0;

@@ -25,6 +25,11 @@ ED_PAIR_DTYPE = np.dtype([
     ("rhs_read", "<u4"), ("rhs_begin", "<u4"), ("rhs_len", "<u4"),
     ("strand", "<u4"), ("reserved", "<u4")])
 
+ALIGN_PAIR_DTYPE = np.dtype([
+    ("query_read", "<u4"), ("query_begin", "<u4"), ("query_len", "<u4"),
+    ("target_read", "<u4"), ("target_begin", "<u4"), ("target_len", "<u4"),
+    ("strand", "<u4"), ("reserved", "<u4")])
+
 RVN_OK, RVN_EINVAL, RVN_ENODEVICE, RVN_EHIP, RVN_ENOMEM = 0, -1, -2, -3, -4
 
 # The C ABI as ctypes sees it: name -> (restype, argtypes), one entry per symbol of include/raven_hip.h (tests/test_abi.py
@@ -84,6 +89,11 @@ _SIGNATURES = {
     "rvn_pile_add_layers": (_i32, [_vp, _vp, _u32, _u32, _vp, _u64]),
     "rvn_pile_add_kmers_batch": (_i32, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "rvn_edit_distance_batch": (_i32, [_vp, _vp, _vp, _u32, _vp, _pdbl, _pu64]),
+    "rvn_align_path_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp]),
+    "rvn_paths_info": (_i32, [_vp, _pu32, _pu64, _pu64, _pu32]),
+    "rvn_paths_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "rvn_paths_fetch_ops": (_i32, [_vp, _vp, _vp]),
+    "rvn_paths_destroy": (None, [_vp]),
     "rvn_poa_consensus_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _i32, _i32, _i32, _vp,
                                        _vp, _vp, _vp, _pdbl]),
     "rvn_polish_round": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
@@ -969,6 +979,32 @@ class Engine:
         _check(lib().rvn_edit_distance_batch(self._h, reads._h, _p(pairs), pairs.shape[0], _p(out), C.byref(ms),
                                              C.byref(cells)))
         return out, ms.value, cells.value
+
+    # -- edlibAlign(NW, TASK_PATH), batched ---------------------------------------------------------
+    def align_paths(self, queries: Reads, targets: Reads, pairs: np.ndarray, ops=False):
+        """rvn_align_path_batch.  pairs: array of ALIGN_PAIR_DTYPE.  Returns (uint32 distances — 0xFFFFFFFF: not aligned —,
+        uint64 run_offsets[n + 1], uint32 runs: count << 2 | op in alignment order, number of pairs not aligned); with
+        ops=True instead of the runs (uint64 op_offsets[n + 1], uint8 ops: edlib's alignment bytes, expanded on the device)."""
+        pairs = np.ascontiguousarray(pairs, dtype=ALIGN_PAIR_DTYPE)
+        h = C.c_void_p()
+        L = lib()
+        _check(L.rvn_align_path_batch(self._h, queries._h, targets._h, _p(pairs), pairs.shape[0], C.byref(h)))
+        try:
+            n, n_runs, n_ops, n_bad = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+            _check(L.rvn_paths_info(h, C.byref(n), C.byref(n_runs), C.byref(n_ops), C.byref(n_bad)))
+            dist = np.zeros(n.value, dtype=np.uint32)
+            if ops:
+                off = np.zeros(n.value + 1, dtype=np.uint64)
+                out = np.zeros(n_ops.value, dtype=np.uint8)
+                _check(L.rvn_paths_fetch(h, _p(dist), None, None))
+                _check(L.rvn_paths_fetch_ops(h, _p(off), _p(out) if n_ops.value else None))
+            else:
+                off = np.zeros(n.value + 1, dtype=np.uint64)
+                out = np.zeros(n_runs.value, dtype=np.uint32)
+                _check(L.rvn_paths_fetch(h, _p(dist), _p(off), _p(out) if n_runs.value else None))
+            return dist, off, out, int(n_bad.value)
+        finally:
+            L.rvn_paths_destroy(h)
 
     # -- racon Window::GenerateConsensus, batched --------------------------------------------------
     def poa_consensus_batch(self, windows, m=3, n=-5, g=-4, trim=True):
