@@ -50,6 +50,20 @@ int rvn_test_nw_breakpoints(const uint64_t* t_words, uint32_t t_len, const uint6
 /* Pile::FindChimericRegions (slopes.h, the __host__ __device__ code the kernel runs) on one coverage array: out = (begin,
  * end) cell pairs; returns their number, -5 if a capacity was exceeded */
 int64_t rvn_test_find_chimeric_regions(const uint16_t* data, uint32_t size, uint32_t* out, uint64_t cap_pairs);
+/* TrimAndAnnotatePiles (pile.hip) ON THE DEVICE for a crafted coverage CSR: the hook makes an engine of its own (device 0),
+ * lays out n piles of offsets[i + 1] - offsets[i] cells each (below 2^28) as a pass does, copies data[offsets[0] ..
+ * offsets[n]) into them and calls what rvn_pass1_trim_and_annotate and rvn_pass1_find_chimeric_regions call — it launches
+ * no kernel itself.  coverage: the threshold of Pile::FindValidRegion (<= 65535).  chimeric_mode: 0 = one wave per pile
+ * (what ships), 1 = one thread per pile (otherwise behind RVN_CHIMERIC_PER_THREAD).  skip_trim != 0: the trim does not run
+ * (begin / end / median / invalid are not written and may be NULL) and FindChimericRegions sees the data as given.
+ * invalid_in (nullable, n flags): the piles FindChimericRegions skips; NULL = the trim's own flags, or none when the trim
+ * was skipped.  Outputs: data_after (nullable) = the cells after the trim, laid out as data; begin / end (cells), median,
+ * invalid = per pile, as rvn_pass1_trim_and_annotate; region_offsets[n + 1] and *regions = CSR of (begin, end) cell pairs,
+ * *regions malloc'ed (rvn_free).  n == 0 or no cells at all: RVN_OK, region_offsets all 0.  RVN_EINVAL for a NULL
+ * argument, another chimeric_mode, descending offsets. */
+int rvn_test_piles_annotate(const uint16_t* data, const uint64_t* offsets, uint32_t n, uint32_t coverage, int chimeric_mode,
+                            const uint8_t* invalid_in, int skip_trim, uint16_t* data_after, uint32_t* begin, uint32_t* end,
+                            uint16_t* median, uint8_t* invalid, uint32_t* region_offsets, uint32_t** regions);
 /* OverlapUpdate + GetOverlapType (overlap_rules.h, the __host__ __device__ code the kernels run) on a list: ok[i] =
  * OverlapUpdate result (the overlap is updated in place when ok), type[i] = GetOverlapType of the updated overlap */
 int rvn_test_overlap_update_and_type(rvn_overlap* overlaps, uint64_t n, const uint32_t* pile_begin, const uint32_t* pile_end,

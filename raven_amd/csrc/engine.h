@@ -491,11 +491,16 @@ void piles_init(Engine& e, const ReadsDev& r, PileState& ps);
 void piles_merge(Engine& e, const ReadsDev& r, const MapOut& mo, u32 kmax, PileState& ps);
 // Pile::FindValidRegion(coverage) + FindMedian on every pile, in place in HBM (pile.hip); host output arrays of n
 void piles_trim_and_median(Engine& e, PileState& ps, u32 coverage, u32* h_begin, u32* h_end, u16* h_median, u8* h_invalid);
-// Pile::FindChimericRegions of every valid pile on the coverage in HBM (pile.hip): CSR of (begin, end) cell pairs
+// Pile::FindChimericRegions of every valid pile on the coverage in HBM (pile.hip): CSR of (begin, end) cell pairs.
+// kernel: which of the two kernels runs — kChimericByKnob = one wave per pile unless RVN_CHIMERIC_PER_THREAD is set (a
+// knob(): the product library always takes the wave kernel); the other two values are for the test hook
+// (rvn_test_piles_annotate), which runs both on the same piles.
+enum ChimericKernel { kChimericByKnob = -1, kChimericWave = 0, kChimericPerThread = 1 };
 void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, std::vector<u32>& h_off,
-                                 std::vector<u32>& h_regions);
+                                 std::vector<u32>& h_regions, ChimericKernel kernel = kChimericByKnob);
 // the same with the flags and the result in HBM: d_roff[n + 1], regions = (begin, end) pairs; returns the number of pairs
-u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_invalid, DevBuf& roff, DevBuf& regions);
+u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_invalid, DevBuf& roff, DevBuf& regions,
+                                    ChimericKernel kernel = kChimericByKnob);
 // Pile::AddKmers for reads [first_read, first_read + n_reads) (pile.hip)
 void pile_add_kmers_batch(Engine& e, const ReadsDev& r, const u32* h_pos, const u64* h_pos_off, u32 n_reads,
                           u32 first_read, u8* h_out, const u64* h_out_off);

@@ -630,7 +630,8 @@ __global__ void chimeric_gather_kernel(const u32* __restrict__ out_tmp, const u6
 
 // d_invalid: the piles' is_invalid flags (from piles_trim_and_median) in HBM; the CSR stays there: roff = u32[n + 1],
 // regions = (begin, end) cell pairs.  Returns the number of pairs.
-u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, DevBuf& roff, DevBuf& regions) {
+u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, DevBuf& roff, DevBuf& regions,
+                                    ChimericKernel kernel) {
   hipStream_t s = e.stream;
   const u32 n = ps.n;
   u32* d_roff = roff.get<u32>(static_cast<size_t>(n) + 2);
@@ -646,7 +647,8 @@ u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, D
   u32* d_cnt = e.tmp_e.get<u32>(static_cast<size_t>(n) + 16);
   u32* d_ovf = d_cnt + n + 8;
   RVN_HIP(hipMemsetAsync(d_ovf, 0, 4, s));
-  if (knob("RVN_CHIMERIC_PER_THREAD"))  // (the earlier layout: one thread per pile; kept for comparisons)
+  if (kernel == kChimericByKnob) kernel = knob("RVN_CHIMERIC_PER_THREAD") ? kChimericPerThread : kChimericWave;
+  if (kernel == kChimericPerThread)  // (the earlier layout: one thread per pile; kept for comparisons)
     RVN_KLAUNCH(kKPileTrim, pile_chimeric_kernel<<<div_up(n, 64), 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
                                                                              d_slopes, d_tmp, d_out, d_cnt, d_ovf));
   else
@@ -667,7 +669,7 @@ u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, D
 
 // h_invalid: the piles' is_invalid flags (from piles_trim_and_median); h_off[n + 1] / regions: CSR of (begin, end) cell pairs
 void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, std::vector<u32>& h_off,
-                                 std::vector<u32>& h_regions) {
+                                 std::vector<u32>& h_regions, ChimericKernel kernel) {
   hipStream_t s = e.stream;
   const u32 n = ps.n;
   h_off.assign(static_cast<size_t>(n) + 1, 0);
@@ -675,7 +677,7 @@ void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, 
   if (n == 0 || ps.pile_words == 0) return;
   u8* d_inv = e.tmp_a.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemcpyAsync(d_inv, h_invalid, n, hipMemcpyHostToDevice, s));
-  const u32 total = piles_find_chimeric_regions_dev(e, ps, d_inv, e.tmp_f, e.sort_tmp);
+  const u32 total = piles_find_chimeric_regions_dev(e, ps, d_inv, e.tmp_f, e.sort_tmp, kernel);
   RVN_HIP(hipMemcpyAsync(h_off.data(), e.tmp_f.ptr, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToHost, s));
   h_regions.assign(2ULL * total, 0);
   if (total) RVN_HIP(hipMemcpyAsync(h_regions.data(), e.sort_tmp.ptr, 2ULL * total * 4, hipMemcpyDeviceToHost, s));

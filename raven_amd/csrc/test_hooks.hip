@@ -300,6 +300,59 @@ static int nw_breakpoints_device(const uint64_t* t_words, uint32_t t_len, const 
   return r;
 }
 
+// TrimAndAnnotatePiles on a crafted coverage CSR, on the device, through the functions the C ABI calls (pile.hip:
+// piles_init, piles_trim_and_median, piles_find_chimeric_regions) in an engine of its own (device 0).  No kernel is
+// launched from here.
+int rvn_test_piles_annotate(const uint16_t* data, const uint64_t* offsets, uint32_t n, uint32_t coverage, int chimeric_mode,
+                            const uint8_t* invalid_in, int skip_trim, uint16_t* data_after, uint32_t* begin, uint32_t* end,
+                            uint16_t* median, uint8_t* invalid, uint32_t* region_offsets, uint32_t** regions) {
+  if (!offsets || !region_offsets || !regions || (chimeric_mode != 0 && chimeric_mode != 1) || coverage > 65535)
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_piles_annotate: bad argument");
+  *regions = nullptr;
+  const u64 total = offsets[n] - offsets[0];
+  if ((total && !data) || (!skip_trim && n && (!begin || !end || !median || !invalid)))
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_piles_annotate: NULL argument");
+  for (u32 i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= (1u << 28))
+      return fail(RVN_EINVAL, "[raven_hip] rvn_test_piles_annotate: offsets must ascend, piles below 2^28 cells");
+  std::memset(region_offsets, 0, (static_cast<size_t>(n) + 1) * 4);
+  auto empty = [&]() -> int {
+    *regions = static_cast<uint32_t*>(std::malloc(4));
+    return *regions ? RVN_OK : fail(RVN_ENOMEM, "[raven_hip] out of host memory");
+  };
+  if (n == 0) return empty();
+  rvn_engine* h = nullptr;
+  int r = rvn_engine_create(&h, 15, 5, 500, 4, 100, 10000, 0);
+  if (r != RVN_OK) return r;
+  r = guarded(&h->e, [&]() -> int {
+    Engine& e = h->e;
+    ReadsDev rd;  // lengths only: a pile is (length >> 4) cells (as rvn_pile_add_layers lays out its one pile)
+    rd.n = n;
+    rd.h_len.resize(n);
+    for (u32 i = 0; i < n; ++i) rd.h_len[i] = static_cast<u32>(offsets[i + 1] - offsets[i]) << 4;
+    PileState ps;
+    piles_init(e, rd, ps);
+    if (total) RVN_HIP(hipMemcpy(ps.pile_data.ptr, data + offsets[0], total * 2, hipMemcpyHostToDevice));
+    std::vector<u8> inv(n, 0);
+    if (!skip_trim) {
+      piles_trim_and_median(e, ps, coverage, begin, end, median, invalid);
+      inv.assign(invalid, invalid + n);
+    }
+    if (invalid_in) inv.assign(invalid_in, invalid_in + n);
+    if (data_after && total) RVN_HIP(hipMemcpy(data_after, ps.pile_data.ptr, total * 2, hipMemcpyDeviceToHost));
+    std::vector<u32> off, reg;
+    piles_find_chimeric_regions(e, ps, inv.data(), off, reg, chimeric_mode ? kChimericPerThread : kChimericWave);
+    std::memcpy(region_offsets, off.data(), off.size() * 4);
+    auto* out = static_cast<uint32_t*>(std::malloc((reg.size() + 1) * 4));
+    if (!out) return fail(RVN_ENOMEM, "[raven_hip] out of host memory");
+    if (!reg.empty()) std::memcpy(out, reg.data(), reg.size() * 4);
+    *regions = out;
+    return RVN_OK;
+  });
+  rvn_engine_destroy(h);
+  return r;
+}
+
 int rvn_test_nw_breakpoints(const uint64_t* t_words, uint32_t t_len, const uint64_t* r_words, uint32_t r_len,
                             uint32_t t_begin, uint32_t n, uint32_t q_begin, uint32_t m, int rc, uint32_t w, uint32_t k,
                             int force_r, uint32_t* recs, uint32_t* distance, uint32_t* band) {

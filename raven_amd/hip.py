@@ -182,6 +182,7 @@ _TEST_SIGNATURES = {
     "rvn_test_nw_breakpoints": (_i32, [_vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _i32, _u32, _u32, _i32, _vp,
                                        _vp, _vp]),
     "rvn_test_find_chimeric_regions": (_i64, [_vp, _u32, _vp, _u64]),
+    "rvn_test_piles_annotate": (_i32, [_vp, _vp, _u32, _u32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _pp]),
     "rvn_test_overlap_update_and_type": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
     "rvn_test_parse_file": (_i32, [_cstr, _i32, _u32, _i32, _u64, _pp, _pp, _pp, _pu32, _pp, _vp]),
     "rvn_test_inflate_fast": (_i32, [_vp, _u64, _vp, _u64, _u64, _vp]),
@@ -1184,6 +1185,43 @@ def test_find_chimeric_regions(data):
     if n < 0:
         raise ValueError("rvn_test_find_chimeric_regions: %d" % n)
     return out[:2 * n].reshape(-1, 2).copy()
+
+
+def test_piles_annotate(data, offsets, coverage=4, per_thread=False, invalid=None, skip_trim=False):
+    """TrimAndAnnotatePiles on the DEVICE for a crafted coverage CSR (rvn_test_piles_annotate: the functions behind
+    Pass1.trim_and_annotate / find_chimeric_regions in an engine of its own).  per_thread: the one-thread-per-pile
+    chimeric kernel instead of the wave kernel; invalid: the piles FindChimericRegions skips (None: the trim's flags);
+    skip_trim: FindChimericRegions on the data as given.  Returns dict(data (after the trim), begin, end, median, invalid
+    (all None when the trim was skipped), region_offsets[n + 1], regions: one (k, 2) uint32 array per pile)."""
+    d = np.ascontiguousarray(data, dtype=np.uint16)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = off.shape[0] - 1
+    assert n >= 0 and int(off[-1]) - int(off[0]) <= d.shape[0] - int(off[0])
+    inv_in = None if invalid is None else np.ascontiguousarray(invalid, dtype=np.uint8)
+    assert inv_in is None or inv_in.shape[0] == n
+    after = np.zeros(int(off[-1]) - int(off[0]), dtype=np.uint16)
+    b, e = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    m, inv = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint8)
+    roff = np.zeros(n + 1, dtype=np.uint32)
+    ptr = C.c_void_p()
+    T = test_lib()
+    rc = T.rvn_test_piles_annotate(_p(d), _p(off), n, int(coverage), int(per_thread), _p(inv_in), int(skip_trim), _p(after),
+                                   _p(b), _p(e), _p(m), _p(inv), _p(roff), C.byref(ptr))
+    if rc != RVN_OK:
+        msg = T.rvn_last_error().decode(errors="replace")
+        if rc == RVN_EINVAL:
+            raise ValueError(msg)
+        raise RavenHipError("rc=%d: %s" % (rc, msg))
+    total = int(roff[-1])
+    try:
+        flat = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint32)), shape=(max(2 * total, 1),))[:2 * total].copy()
+    finally:
+        T.rvn_free(ptr)
+    flat = flat.reshape(-1, 2)
+    regions = [flat[int(roff[i]):int(roff[i + 1])] for i in range(n)]
+    if skip_trim:
+        return dict(data=after, begin=None, end=None, median=None, invalid=None, region_offsets=roff, regions=regions)
+    return dict(data=after, begin=b, end=e, median=m, invalid=inv.astype(bool), region_offsets=roff, regions=regions)
 
 
 def overlap_update_and_type(overlaps, pile_begin, pile_end, pile_invalid):

@@ -6,32 +6,7 @@ import numpy as np
 
 from oracle import oracle
 from raven_amd import hip
-
-
-def _profile(rng, cells):
-    base = int(rng.integers(8, 60))
-    d = np.full(cells, base, dtype=np.int64)
-    d += rng.integers(-2, 3, size=cells)
-    for _ in range(int(rng.integers(0, 5))):  # pits: coverage drops (chimeric junctions), various widths / depths
-        c, wdt = int(rng.integers(60, cells - 60)), int(rng.integers(1, 40))
-        depth = rng.choice([0.05, 0.2, 0.45, 0.6])
-        lo, hi = max(0, c - wdt), min(cells, c + wdt)
-        d[lo:hi] = (d[lo:hi] * depth).astype(np.int64)
-    for _ in range(int(rng.integers(0, 4))):  # spikes (repeats)
-        c, wdt = int(rng.integers(60, cells - 60)), int(rng.integers(3, 80))
-        d[max(0, c - wdt):min(cells, c + wdt)] *= int(rng.integers(2, 5))
-    if rng.random() < 0.5:  # ramps at the ends, as real piles have
-        r = int(rng.integers(10, 60))
-        d[:r] = (d[:r] * np.linspace(0.1, 1, r)).astype(np.int64)
-        d[-r:] = (d[-r:] * np.linspace(1, 0.1, r)).astype(np.int64)
-    if rng.random() < 0.5:  # zeroed outside the valid region (UpdateValidRegion)
-        a, b = int(rng.integers(0, 30)), int(rng.integers(0, 30))
-        d[:a] = 0
-        if b:
-            d[-b:] = 0
-    if rng.random() < 0.1:
-        d[rng.integers(0, cells, size=5)] = 65535  # saturated cells: the clamp matters
-    return np.clip(d, 0, 65535).astype(np.uint16)
+from tests.pile_cases import profile as _profile  # (shared with the crafted piles of the device tests)
 
 
 def test_find_chimeric_regions_matches_the_restatement_of_pile_cc():
