@@ -98,6 +98,36 @@ int rvn_test_freelist(uint64_t size, uint64_t grain, const int64_t* ops, uint32_
  * Returns 0, RVN_EINVAL for a NULL argument or another W. */
 int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off, const uint32_t* pairs, uint32_t n,
                      const uint32_t* kmax, int W, uint32_t* out);
+/* The probe branch of Map's match stage (map.hip: index_build_table, match_count_kernel, the scan, match_emit_kernel, the
+ * gather of the segment offsets — the one function map_batch_impl calls) ON THE DEVICE with the query sketch taken from
+ * the host instead of from reads.  h: an engine of THIS library whose index is built (rvn_shard_index_build or
+ * rvn_engine_minimize; occurrence and the option index_direct_min_keys as set on it).  q_values (below 4^k) / q_origins
+ * (id << 32 | pos << 1 | strand): the n_query minimizers of n_reads query reads in (read, position) order, read i's at
+ * [q_read_off[i], q_read_off[i + 1]), q_read_off[0] = 0, q_read_off[n_reads] = n_query.  Outputs, as they are BEFORE the
+ * chain stage sorts them: *group / *positions = the matches in ram's emission order (query minimizer, then run order),
+ * malloc'ed (rvn_free); seg_off[n_reads + 1] = per-read offsets into them; filtered[n_query] = 1 where the occurrence
+ * filter skipped the minimizer; *n_matches.  No query minimizers or an empty index: RVN_OK and no matches (Map returns
+ * before the stage).  RVN_EINVAL for a NULL argument, offsets that do not ascend from 0 to n_query, a value of more than 2k
+ * bits.  It launches no kernel itself. */
+int rvn_test_match_probe(rvn_engine* h, const uint64_t* q_values, const uint64_t* q_origins, uint64_t n_query,
+                         const uint32_t* q_read_off, uint32_t n_reads, int avoid_equal, int avoid_symmetric,
+                         uint64_t** group, uint64_t** positions, uint64_t* seg_off, uint8_t* filtered,
+                         uint64_t* n_matches);
+/* The device-wide stable LSD radix sort (radix_sort.hip) on n host pairs, in place: variant 0 = radix_sort_pairs_u32_u64
+ * (the index of k <= 15), 1 = _u64_u64 (k >= 16), 2 = _u32_u32; keys and values travel as 64-bit words whatever the variant
+ * (RVN_EINVAL if one does not fit).  key_bits (0 .. 32 or 64): the sort orders by the 8-bit digits that hold bits [0, key_bits), i.e. by
+ * the low ceil(key_bits / 8) bytes, and leaves the order by the bytes above alone (callers' keys have no bits there);
+ * skip_constant_digits as the function's argument of that name (the index sorts with 0).  The hook makes an engine of its
+ * own (device 0) for the stream and the scratch, copies, and calls the one function — it launches no kernel itself. */
+int rvn_test_radix_sort_pairs(int variant, uint64_t* keys, uint64_t* values, uint64_t n, int key_bits,
+                              int skip_constant_digits);
+/* The device-wide exclusive prefix sum (scan.hip) of n host values: variant 0 = exclusive_scan_u32_u64, 1 = _u32_u32,
+ * 2 = _u8_u32 (RVN_EINVAL if a value does not fit the input type); out[n + 1], out[n] = the total.  in_offset_items /
+ * out_offset_items (<= 64): the device arrays start that many ELEMENTS behind a 256-byte boundary, so that an offset that is
+ * no multiple of 16 bytes takes the kernels' element-wise path instead of their 16-byte accesses.  Engine of its own
+ * (device 0), one call, no kernel launched from here. */
+int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_t in_offset_items,
+                            uint32_t out_offset_items, uint64_t* out);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

@@ -17,6 +17,10 @@
 
 #include "engine.h"
 #include "wave.h"
+#ifdef RVN_TEST_HOOKS
+#include "../../include/raven_hip_test.h"
+#include "abi.h"
+#endif
 
 namespace rvn {
 
@@ -1253,6 +1257,42 @@ void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, Map
 
 namespace {
 
+// The probe branch of Map's match stage: every minimizer of the query sketch qs (nq = qs.count > 0 minimizers of nr reads,
+// qs.read_off their per-read offsets) looked up in the engine's index (m > 0; its table is built here if it is not yet).
+// The matches land in e.m_grp[0] / e.m_pos[0] in (query minimizer, run) order, their per-read offsets in seg_off[nr + 1]
+// (not written when there is no match); filt (nullable): per-minimizer "skipped by the occurrence filter".  Returns the
+// number of matches.  Called by map_batch_impl and by the test hook rvn_test_match_probe below.
+template <typename V>
+u64 match_probe(Engine& e, const Sketch& qs, u32 nr, bool avoid_equal, bool avoid_symmetric, u8* filt, u64* seg_off) {
+  hipStream_t s = e.stream;
+  Index& ix = e.index;
+  index_build_table(e);
+  const u64 nq = qs.count;
+  StageTimer t(e, StageTimes::kMatch);
+  u32* q_start = e.q_start.get<u32>(nq + 1);
+  u32* q_n = e.tmp_a.get<u32>(nq + 1);
+  u32* q_cnt = e.q_cnt.get<u32>(nq + 1);
+  u64* m_off = e.m_off.get<u64>(nq + 2);
+  RVN_KLAUNCH(kKMatchCount, match_count_kernel<V><<<div_up(nq, 256), 256, 0, s>>>(
+      qs.val.as<V>(), qs.org.as<u64>(), nq, ix.u_val.as<V>(), ix.u_start.as<u32>(), ix.table.as<u32>(), ix.shift,
+      static_cast<u32>(ix.u), ix.s_org[ix.cur].as<u64>(), ix.occurrence, avoid_equal, avoid_symmetric, q_start, q_n,
+      q_cnt, filt, ix.direct_built ? ix.direct.as<u64>() : nullptr));
+  exclusive_scan_u32_u64(q_cnt, m_off, nq, e.scan_tmp, s);
+  const u64 H = read_back(e, m_off + nq, 8);
+  if (H) {
+    u64* g0 = e.m_grp[0].get<u64>(H + 1);
+    u64* p0 = e.m_pos[0].get<u64>(H + 1);
+    e.m_grp[1].reserve((H + 1) * 8);
+    e.m_pos[1].reserve((H + 1) * 8);
+    RVN_KLAUNCH(kKMatchEmit, match_emit_kernel<<<div_up(nq, 256), 256, 0, s>>>(qs.org.as<u64>(), nq, ix.s_org[ix.cur].as<u64>(), q_start,
+                                                      q_n, m_off, avoid_equal, avoid_symmetric, g0, p0));
+    RVN_KLAUNCH(kKGather, gather_u64_by_u32_kernel<<<div_up(nr + 1, 256), 256, 0, s>>>(
+                              e.m_off.as<u64>(), qs.read_off.as<u32>(), seg_off, nr + 1));
+  }
+  t.stop();
+  return H;
+}
+
 template <typename V>
 void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoid_equal, bool avoid_symmetric,
                     bool minhash, bool want_filtered, MapOut& out) {
@@ -1301,7 +1341,6 @@ void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoi
   }
   Sketch& qs = e.query_sketch;
   if (!join) {
-    index_build_table(e);
   {
     StageTimer t(e, StageTimes::kQuery);
     const bool ready = e.query_ready && e.query_ready_first == first && e.query_ready_last == last &&
@@ -1322,35 +1361,8 @@ void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoi
     }
     return;
   }
-  {
-    StageTimer t(e, StageTimes::kMatch);
-    u32* q_start = e.q_start.get<u32>(nq + 1);
-    u32* q_n = e.tmp_a.get<u32>(nq + 1);
-    u32* q_cnt = e.q_cnt.get<u32>(nq + 1);
-    u8* filt = want_filtered ? out.filtered.get<u8>(nq + 1) : nullptr;
-    u64* m_off = e.m_off.get<u64>(nq + 2);
-    RVN_KLAUNCH(kKMatchCount, match_count_kernel<V><<<div_up(nq, 256), 256, 0, s>>>(
-        qs.val.as<V>(), qs.org.as<u64>(), nq, ix.u_val.as<V>(), ix.u_start.as<u32>(), ix.table.as<u32>(), ix.shift,
-        static_cast<u32>(ix.u), ix.s_org[ix.cur].as<u64>(), ix.occurrence, avoid_equal, avoid_symmetric, q_start, q_n,
-        q_cnt, filt, ix.direct_built ? ix.direct.as<u64>() : nullptr));
-    exclusive_scan_u32_u64(q_cnt, m_off, nq, e.scan_tmp, s);
-    H = read_back(e, m_off + nq, 8);
-    out.n_matches = H;
-    e.c_matches += H;
-    if (H) {
-      u64* g0 = e.m_grp[0].get<u64>(H + 1);
-      u64* p0 = e.m_pos[0].get<u64>(H + 1);
-      e.m_grp[1].reserve((H + 1) * 8);
-      e.m_pos[1].reserve((H + 1) * 8);
-      RVN_KLAUNCH(kKMatchEmit, match_emit_kernel<<<div_up(nq, 256), 256, 0, s>>>(qs.org.as<u64>(), nq, ix.s_org[ix.cur].as<u64>(), q_start,
-                                                        q_n, m_off, avoid_equal, avoid_symmetric, g0, p0));
-    }
-    if (H) {
-      RVN_KLAUNCH(kKGather, gather_u64_by_u32_kernel<<<div_up(nr + 1, 256), 256, 0, s>>>(
-                                e.m_off.as<u64>(), qs.read_off.as<u32>(), seg_off, nr + 1));
-    }
-    t.stop();
-  }
+  H = match_probe<V>(e, qs, nr, avoid_equal, avoid_symmetric, want_filtered ? out.filtered.get<u8>(nq + 1) : nullptr, seg_off);
+  e.c_matches += H;
   }  // !join
   out.n_matches = H;
   chain_matches(e, r, first, last, H, out);
@@ -1446,4 +1458,82 @@ void map_batch(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoid_equ
   else map_batch_impl<u32>(e, r, first, last, avoid_equal, avoid_symmetric, minhash, want_filtered, out);
 }
 
+#ifdef RVN_TEST_HOOKS
+// rvn_test_match_probe (include/raven_hip_test.h): match_probe on a query sketch given by the host.  Every argument that a
+// kernel would index with is checked here; no kernel is launched from here.
+static int test_match_probe(Engine& e, const u64* q_values, const u64* q_origins, u64 nq, const u32* q_read_off, u32 nr,
+                     bool avoid_equal, bool avoid_symmetric, u64** grp, u64** pos, u64* seg_off, u8* filtered, u64* n_matches) {
+  *grp = *pos = nullptr;
+  *n_matches = 0;
+  std::memset(seg_off, 0, (static_cast<size_t>(nr) + 1) * 8);
+  if (nq) std::memset(filtered, 0, nq);
+  if (nq >= (1ULL << 32)) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: >= 2^32 query minimizers");
+  if (q_read_off[0] != 0 || q_read_off[nr] != nq) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: offsets must run from 0 to n_query");
+  for (u32 i = 0; i < nr; ++i)
+    if (q_read_off[i + 1] < q_read_off[i]) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: offsets must ascend");
+  const u64 limit = 1ULL << (2 * e.k);  // (k <= 31)
+  for (u64 i = 0; i < nq; ++i)
+    if (q_values[i] >= limit) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: value of more than 2k bits");
+  auto empty = [](u64** p) {
+    *p = static_cast<u64*>(std::malloc(8));
+    if (!*p) throw std::bad_alloc();
+  };
+  if (nq == 0 || e.index.m == 0) {  // (map_batch_impl returns before the match stage)
+    empty(grp);
+    empty(pos);
+    return RVN_OK;
+  }
+  Sketch& qs = e.query_sketch;
+  e.query_ready = false;
+  qs.first = 0;
+  qs.last = nr;
+  qs.count = nq;
+  if (e.val64) {
+    RVN_HIP(hipMemcpy(qs.val.get<u64>(nq + 1), q_values, nq * 8, hipMemcpyHostToDevice));
+  } else {
+    std::vector<u32> v32(nq);
+    for (u64 i = 0; i < nq; ++i) v32[i] = static_cast<u32>(q_values[i]);
+    RVN_HIP(hipMemcpy(qs.val.get<u32>(nq + 1), v32.data(), nq * 4, hipMemcpyHostToDevice));
+  }
+  RVN_HIP(hipMemcpy(qs.org.get<u64>(nq + 1), q_origins, nq * 8, hipMemcpyHostToDevice));
+  RVN_HIP(hipMemcpy(qs.read_off.get<u32>(static_cast<size_t>(nr) + 1), q_read_off, (static_cast<size_t>(nr) + 1) * 4, hipMemcpyHostToDevice));
+  u8* d_filt = e.map_out.filtered.get<u8>(nq + 1);
+  u64* d_seg = e.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+  const u64 H = e.val64 ? match_probe<u64>(e, qs, nr, avoid_equal, avoid_symmetric, d_filt, d_seg)
+                        : match_probe<u32>(e, qs, nr, avoid_equal, avoid_symmetric, d_filt, d_seg);
+  RVN_HIP(hipMemcpy(filtered, d_filt, nq, hipMemcpyDeviceToHost));
+  *grp = static_cast<u64*>(std::malloc((H + 1) * 8));
+  *pos = static_cast<u64*>(std::malloc((H + 1) * 8));
+  if (!*grp || !*pos) throw std::bad_alloc();
+  if (H) {
+    RVN_HIP(hipMemcpy(*grp, e.m_grp[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(*pos, e.m_pos[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(seg_off, d_seg, (static_cast<size_t>(nr) + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  *n_matches = H;
+  return RVN_OK;
+}
+#endif  // RVN_TEST_HOOKS
+
 }  // namespace rvn
+
+#ifdef RVN_TEST_HOOKS
+extern "C" int rvn_test_match_probe(rvn_engine* h, const uint64_t* q_values, const uint64_t* q_origins, uint64_t n_query,
+                                    const uint32_t* q_read_off, uint32_t n_reads, int avoid_equal, int avoid_symmetric,
+                                    uint64_t** group, uint64_t** positions, uint64_t* seg_off, uint8_t* filtered,
+                                    uint64_t* n_matches) {
+  using namespace rvn;
+  const bool ok = h && q_read_off && group && positions && seg_off && n_matches && !(n_query && (!q_values || !q_origins || !filtered));
+  return guarded(h, ok, "[raven_hip] rvn_test_match_probe: NULL argument", [&](Engine& e) -> int {
+    try {
+      return test_match_probe(e, q_values, q_origins, n_query, q_read_off, n_reads, avoid_equal != 0, avoid_symmetric != 0, group,
+                              positions, seg_off, filtered, n_matches);
+    } catch (...) {
+      std::free(*group);
+      std::free(*positions);
+      *group = *positions = nullptr;
+      throw;
+    }
+  });
+}
+#endif  // RVN_TEST_HOOKS

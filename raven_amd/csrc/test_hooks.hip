@@ -2,6 +2,7 @@
 // into libraven_hip_test.so (TEST INFRASTRUCTURE).
 #include <chrono>
 #include <cstring>
+#include <vector>
 
 #include "../../include/raven_hip_test.h"
 #include "abi.h"
@@ -15,6 +16,72 @@
 #include "slopes.h"
 
 using namespace rvn;
+
+namespace {
+
+// The device-wide primitives (radix_sort.hip, scan.hip) on host arrays, in an engine of its own (device 0) for the stream
+// and the scratch; f(Engine&) does the copies and the one call.
+template <typename F>
+int with_own_engine(F f) {
+  rvn_engine* h = nullptr;
+  int r = rvn_engine_create(&h, 15, 5, 500, 4, 100, 10000, 0);
+  if (r != RVN_OK) return r;
+  r = guarded(&h->e, [&]() -> int { return f(h->e); });
+  rvn_engine_destroy(h);
+  return r;
+}
+
+template <typename K, typename V, typename Sort>
+int radix_sort_pairs_host(Engine& e, uint64_t* keys, uint64_t* values, u64 n, int key_bits, bool skip, Sort sort) {
+  std::vector<K> hk(n);
+  std::vector<V> hv(n);
+  for (u64 i = 0; i < n; ++i) {
+    hk[i] = static_cast<K>(keys[i]);
+    hv[i] = static_cast<V>(values[i]);
+    if (hk[i] != keys[i] || hv[i] != values[i]) return fail(RVN_EINVAL, "[raven_hip] rvn_test_radix_sort_pairs: value too wide for the variant");
+  }
+  DevBuf bk[2], bv[2];
+  K* k0 = bk[0].get<K>(n + 1);
+  K* k1 = bk[1].get<K>(n + 1);
+  V* v0 = bv[0].get<V>(n + 1);
+  V* v1 = bv[1].get<V>(n + 1);
+  if (n) {
+    RVN_HIP(hipMemcpy(k0, hk.data(), n * sizeof(K), hipMemcpyHostToDevice));
+    RVN_HIP(hipMemcpy(v0, hv.data(), n * sizeof(V), hipMemcpyHostToDevice));
+  }
+  const int cur = sort(k0, k1, v0, v1, n, key_bits, e.sort_tmp, e.scan_tmp, e.stream, kKRsUpsweep, kKRsDownsweep, skip);
+  RVN_HIP(rvn_stream_sync(e.stream));
+  if (n) {
+    RVN_HIP(hipMemcpy(hk.data(), cur ? k1 : k0, n * sizeof(K), hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(hv.data(), cur ? v1 : v0, n * sizeof(V), hipMemcpyDeviceToHost));
+  }
+  for (u64 i = 0; i < n; ++i) {
+    keys[i] = hk[i];
+    values[i] = hv[i];
+  }
+  return RVN_OK;
+}
+
+template <typename In, typename Out, typename Scan>
+int exclusive_scan_host(Engine& e, const uint64_t* in, uint64_t* out, u64 n, u32 in_off, u32 out_off, Scan scan) {
+  std::vector<In> hi(n);
+  for (u64 i = 0; i < n; ++i) {
+    hi[i] = static_cast<In>(in[i]);
+    if (hi[i] != in[i]) return fail(RVN_EINVAL, "[raven_hip] rvn_test_exclusive_scan: value too wide for the variant");
+  }
+  DevBuf bi, bo;  // (hipMalloc aligns to at least 256 bytes: the element offsets alone decide the 16-byte alignment)
+  In* d_in = bi.get<In>(n + in_off + 1) + in_off;
+  Out* d_out = bo.get<Out>(n + out_off + 2) + out_off;
+  if (n) RVN_HIP(hipMemcpy(d_in, hi.data(), n * sizeof(In), hipMemcpyHostToDevice));
+  scan(d_in, d_out, n, e.scan_tmp, e.stream);
+  RVN_HIP(rvn_stream_sync(e.stream));
+  std::vector<Out> ho(n + 1);
+  RVN_HIP(hipMemcpy(ho.data(), d_out, (n + 1) * sizeof(Out), hipMemcpyDeviceToHost));
+  for (u64 i = 0; i <= n; ++i) out[i] = ho[i];
+  return RVN_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -363,6 +430,29 @@ int rvn_test_nw_breakpoints(const uint64_t* t_words, uint32_t t_len, const uint6
                                                    recs, distance, band);
   return nw_breakpoints_host(t_words, t_len, r_words, r_len, t_begin, n, q_begin, m, rc, w, k, force_r,
                              reinterpret_cast<NwWindowRec*>(recs), distance, band);
+}
+
+int rvn_test_radix_sort_pairs(int variant, uint64_t* keys, uint64_t* values, uint64_t n, int key_bits, int skip_constant_digits) {
+  const int width = variant == 1 ? 64 : 32;
+  if (variant < 0 || variant > 2 || (n && (!keys || !values)) || key_bits < 0 || key_bits > width || n >= (1ULL << 32))
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_radix_sort_pairs: bad argument");
+  return with_own_engine([&](Engine& e) -> int {
+    const bool skip = skip_constant_digits != 0;
+    if (variant == 0) return radix_sort_pairs_host<u32, u64>(e, keys, values, n, key_bits, skip, radix_sort_pairs_u32_u64);
+    if (variant == 1) return radix_sort_pairs_host<u64, u64>(e, keys, values, n, key_bits, skip, radix_sort_pairs_u64_u64);
+    return radix_sort_pairs_host<u32, u32>(e, keys, values, n, key_bits, skip, radix_sort_pairs_u32_u32);
+  });
+}
+
+int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_t in_offset_items, uint32_t out_offset_items,
+                            uint64_t* out) {
+  if (variant < 0 || variant > 2 || (n && !in) || !out || n >= (1ULL << 32) || in_offset_items > 64 || out_offset_items > 64)
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_exclusive_scan: bad argument");
+  return with_own_engine([&](Engine& e) -> int {
+    if (variant == 0) return exclusive_scan_host<u32, u64>(e, in, out, n, in_offset_items, out_offset_items, exclusive_scan_u32_u64);
+    if (variant == 1) return exclusive_scan_host<u32, u32>(e, in, out, n, in_offset_items, out_offset_items, exclusive_scan_u32_u32);
+    return exclusive_scan_host<u8, u32>(e, in, out, n, in_offset_items, out_offset_items, exclusive_scan_u8_u32);
+  });
 }
 
 int rvn_test_low_complexity(const uint8_t* codes, uint32_t k) { return lc_kmer_passes(codes, k) ? 1 : 0; }

@@ -188,6 +188,9 @@ _TEST_SIGNATURES = {
     "rvn_test_inflate_fast": (_i32, [_vp, _u64, _vp, _u64, _u64, _vp]),
     "rvn_test_freelist": (_i32, [_u64, _u64, _vp, _u32, _vp, _vp]),
     "rvn_test_ed_lane": (_i32, [_vp, _vp, _vp, _u32, _vp, _i32, _vp]),
+    "rvn_test_match_probe": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _i32, _i32, _pp, _pp, _vp, _vp, _pu64]),
+    "rvn_test_radix_sort_pairs": (_i32, [_i32, _vp, _vp, _u64, _i32, _i32]),
+    "rvn_test_exclusive_scan": (_i32, [_i32, _vp, _u64, _u32, _u32, _vp]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1222,6 +1225,108 @@ def test_piles_annotate(data, offsets, coverage=4, per_thread=False, invalid=Non
     if skip_trim:
         return dict(data=after, begin=None, end=None, median=None, invalid=None, region_offsets=roff, regions=regions)
     return dict(data=after, begin=b, end=e, median=m, invalid=inv.astype(bool), region_offsets=roff, regions=regions)
+
+
+def _test_check(rc):
+    if rc != RVN_OK:
+        msg = test_lib().rvn_last_error().decode(errors="replace")
+        if rc == RVN_EINVAL:
+            raise ValueError(msg)
+        raise RavenHipError("rc=%d: %s" % (rc, msg))
+
+
+SORT_VARIANTS = {"u32_u64": 0, "u64_u64": 1, "u32_u32": 2}
+SCAN_VARIANTS = {"u32_u64": 0, "u32_u32": 1, "u8_u32": 2}
+
+
+def test_radix_sort_pairs(variant, keys, values, key_bits, skip_constant_digits=True):
+    """The device-wide radix sort (radix_sort.hip) on host pairs (rvn_test_radix_sort_pairs): variant = a key of
+    SORT_VARIANTS.  Returns (sorted keys, values carried along) as uint64."""
+    k = np.array(keys, dtype=np.uint64)
+    v = np.array(values, dtype=np.uint64)
+    assert k.shape == v.shape and k.ndim == 1
+    _test_check(test_lib().rvn_test_radix_sort_pairs(SORT_VARIANTS[variant], _p(k), _p(v), k.shape[0], int(key_bits),
+                                                     int(skip_constant_digits)))
+    return k, v
+
+
+def test_exclusive_scan(variant, values, in_offset=0, out_offset=0):
+    """The device-wide exclusive prefix sum (scan.hip) of host values (rvn_test_exclusive_scan): variant = a key of
+    SCAN_VARIANTS; in_offset / out_offset = elements by which the device arrays are shifted off their 16-byte alignment.
+    Returns uint64[n + 1] (the last entry = the total)."""
+    a = np.ascontiguousarray(values, dtype=np.uint64)
+    out = np.zeros(a.shape[0] + 1, dtype=np.uint64)
+    _test_check(test_lib().rvn_test_exclusive_scan(SCAN_VARIANTS[variant], _p(a), a.shape[0], int(in_offset), int(out_offset),
+                                                   _p(out)))
+    return out
+
+
+class HookEngine:
+    """TEST INFRASTRUCTURE: an engine made by libraven_hip_test.so (a handle belongs to the library that made it), with
+    what rvn_test_match_probe needs around it: an index from a crafted stream, the occurrence, the probe itself."""
+
+    def __init__(self, k, direct_index=False):
+        T = test_lib()
+        h = C.c_void_p()
+        _test_check(T.rvn_engine_create(C.byref(h), k, 5, 500, 4, 100, 10000, 0))
+        self._h, self.k = h, k
+        if direct_index:  # every index with 2k <= 30 bits gets the direct-address table
+            _test_check(T.rvn_engine_set_option(h, b"index_direct_min_keys", 1, None))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            test_lib().rvn_engine_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def index_build(self, values, origins):
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        origins = np.ascontiguousarray(origins, dtype=np.uint64)
+        _test_check(test_lib().rvn_shard_index_build(self._h, _p(values), _p(origins), values.shape[0], 0))
+
+    def set_occurrence(self, occurrence):
+        _test_check(test_lib().rvn_engine_set_occurrence(self._h, int(occurrence)))
+
+    def count_launches(self, on=True):
+        """Start counting kernel launches per site from zero (on) / stop."""
+        T = test_lib()
+        T.rvn_engine_set_kernel_timing(self._h, int(on))
+        if on:
+            T.rvn_engine_reset_stats(self._h)
+
+    def launches(self):
+        """{site: launches} since count_launches()."""
+        T = test_lib()
+        n = T.rvn_engine_num_kernel_sites()
+        ms, la = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint64)
+        _test_check(T.rvn_engine_kernel_ms(self._h, _p(ms), _p(la), n))
+        return {T.rvn_engine_kernel_site_name(i).decode(): int(la[i]) for i in range(n)}
+
+    def match_probe(self, q_values, q_origins, q_read_off, avoid_equal, avoid_symmetric):
+        """rvn_test_match_probe: (group words, position words, seg_off[n_reads + 1], filtered[n_query])."""
+        qv = np.ascontiguousarray(q_values, dtype=np.uint64)
+        qo = np.ascontiguousarray(q_origins, dtype=np.uint64)
+        off = np.ascontiguousarray(q_read_off, dtype=np.uint32)
+        nr = off.shape[0] - 1
+        assert nr >= 0 and qv.shape == qo.shape
+        seg = np.zeros(nr + 1, dtype=np.uint64)
+        filt = np.zeros(max(qv.shape[0], 1), dtype=np.uint8)
+        pg, pp, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        T = test_lib()
+        _test_check(T.rvn_test_match_probe(self._h, _p(qv), _p(qo), qv.shape[0], _p(off), nr, int(avoid_equal),
+                                           int(avoid_symmetric), C.byref(pg), C.byref(pp), _p(seg), _p(filt), C.byref(n)))
+        try:
+            grp, pos = (np.ctypeslib.as_array(C.cast(x, C.POINTER(C.c_uint64)), shape=(max(n.value, 1),))[:n.value].copy()
+                        for x in (pg, pp))
+        finally:
+            T.rvn_free(pg)
+            T.rvn_free(pp)
+        return grp, pos, seg, filt[:qv.shape[0]]
 
 
 def overlap_update_and_type(overlaps, pile_begin, pile_end, pile_invalid):
