@@ -74,6 +74,8 @@ def lib():
         L.orc_antiqsort.argtypes = [vp, u32]
         L.orc_poa_window.restype = i32
         L.orc_poa_window.argtypes = [vp, vp, vp, vp, vp, u32, i32, i32, i32, i32, vp, u32, C.POINTER(u32)]
+        L.orc_poa_window_stats.restype = i32
+        L.orc_poa_window_stats.argtypes = [vp, vp, vp, vp, vp, u32, i32, i32, i32, vp, vp]
         L.orc_poa_order_check.restype = i32
         L.orc_poa_order_check.argtypes = [vp, vp, vp, vp, u32, i32, i32, i32, vp]
         L.orc_poa_align_score_linear.restype = i32
@@ -387,6 +389,43 @@ def poa_window(layers, begins=None, ends=None, quals=None, m=3, n=-5, g=-4, trim
     if polished < 0:
         raise ValueError("[racon::Window::AddLayer] error: layer begin and end positions are invalid!")
     return out[:n_out.value].copy(), bool(polished)
+
+
+POA_LAYER_STATS = ("nodes", "in_degree", "in_edge_ranks", "tails_below", "off_centre", "band_step", "band_step_min", "rows",
+                   "long_index", "long_degree", "walk_index", "walk_vertical")
+
+
+def poa_window_stats(layers, begins=None, ends=None, quals=None, m=3, n=-5, g=-4):
+    """The graph each layer's alignment meets, built as poa_window(..., device_order=True, end_tie=1) builds it: what a
+    generator of crafted windows is checked against (so that it is never tuned by running a kernel).  Returns a dict:
+    per layer, in the caller's order (the backbone's entry is 0), arrays `nodes` (of the graph the layer is aligned to),
+    `in_degree` (largest among the rows of the layer's subgraph, tails inside it), `in_edge_ranks` (longest in-edge,
+    head rank - tail rank in the device's order), `tails_below` (in-edges cut by the subgraph whose tail ranks below its
+    rank range), `off_centre` (largest distance of the alignment path from the straight band centre), `band_step` /
+    `band_step_min` (largest / smallest difference of 32-column band starts along an in-edge), `rows` (ranks in the
+    subgraph's range), `long_index` / `long_degree` (the longest in-edge's place among its head's in-edges, and that head's
+    in-degree), `walk_index` / `walk_vertical` (the in-edge, as its place among the in-edges of the row with the largest
+    in-degree, through which the layer's own path enters that row, -1 if it does not; 1 if the path passes the row without
+    a base of the layer); for the window `final_nodes`, `final_in_degree` and `agree` (spoa's rules and the device's give the
+    same consensus bytes, trim on and off)."""
+    k = len(layers)
+    off = np.zeros(k + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in layers], out=off[1:])
+    codes = np.concatenate([np.asarray(x, dtype=np.uint8) for x in layers])
+    q = None if quals is None else np.concatenate([np.asarray(x, dtype=np.uint8) for x in quals])
+    blen = len(layers[0])
+    b = np.asarray([0] * k if begins is None else begins, dtype=np.uint32)
+    e = np.asarray([blen - 1] * k if ends is None else ends, dtype=np.uint32)
+    per = np.zeros((k, len(POA_LAYER_STATS)), dtype=np.int64)
+    whole = np.zeros(3, dtype=np.int64)
+    rc = lib().orc_poa_window_stats(_p(codes), _p(q), _p(off), _p(b), _p(e), k, m, n, g, _p(per), _p(whole))
+    if rc == -1:
+        raise ValueError("[racon::Window::AddLayer] error: layer begin and end positions are invalid!")
+    if rc != 0:
+        raise RuntimeError("the device's order rule broke down on this window")
+    out = {name: per[:, i].copy() for i, name in enumerate(POA_LAYER_STATS)}
+    out.update(final_nodes=int(whole[0]), agree=bool(whole[1]), final_in_degree=int(whole[2]))
+    return out
 
 
 def poa_order_check(layers, begins=None, ends=None, m=3, n=-5, g=-4):

@@ -460,9 +460,51 @@ static thread_local int g_order_where = 3;  // diagnostic split of device_order 
 // device order rule broke down.
 // where: 1 = the device's order for the alignments (NW rows, Subgraph rows), 2 = for the consensus, 3 = both (diagnostic
 // split: which of the two decides a tie)
+// What a layer's alignment sees of the graph (orc_poa_window_stats: lets a test generator be asserted to build what it is
+// named after without asking a kernel).  Ranks are the device's order; an in-edge counts where head and tail are both rows
+// of the layer's subgraph (every node for a layer that spans the backbone).
+struct LayerStats {
+  std::int64_t nodes = 0;          // nodes of the graph the layer is aligned to
+  std::int64_t in_degree = 0;      // largest in-degree among the subgraph's rows
+  std::int64_t in_edge_ranks = 0;  // longest in-edge: rank(head) - rank(tail)
+  std::int64_t tails_below = 0;    // in-edges of the subgraph's rows whose tail ranks below the subgraph's rank range
+  std::int64_t off_centre = 0;     // largest distance of the alignment path from the straight band centre, in columns
+  std::int64_t band_step = 0;      // largest difference of 32-column band starts along an in-edge (head - tail)
+  std::int64_t band_step_min = 0;  // smallest (a negative one: the band would step backwards)
+  std::int64_t rows = 0;           // ranks in the subgraph's rank range
+  std::int64_t long_index = 0;     // the longest in-edge's place among its head's in-edges (first one of that length, rows in rank order)
+  std::int64_t long_degree = 0;    // in-degree of that head
+  std::int64_t walk_index = -1;    // the in-edge through which the layer's path enters the row of the largest in-degree (the first such
+                                   // row in rank order), as its place among that row's in-edges; -1: the path does not, or starts there
+  std::int64_t walk_vertical = 0;  // 1: the path passes that row without a base of the layer (a vertical move), 0: with one
+};
+// The band guide restated (raven_amd/csrc/poa.h poa_layer_center with the straight guide poa_layer_linear_way fills in):
+// the layer offset expected at backbone position begin + x, piecewise linear through len * i / 8 at x = span * i / 8.
+static std::int32_t StraightCentre(std::int32_t len, std::int32_t x, std::int32_t span) {
+  x = x < 0 ? 0 : (x > span ? span : x);
+  const std::int32_t seg = (x * 8) / (span > 0 ? span : 1);
+  const std::int32_t s = seg > 7 ? 7 : seg;
+  const std::int32_t x0 = (s * span) / 8, x1 = ((s + 1) * span) / 8;
+  const std::int32_t w0 = static_cast<std::int32_t>(static_cast<std::int64_t>(len) * s / 8);
+  const std::int32_t w1 = s == 7 ? len : static_cast<std::int32_t>(static_cast<std::int64_t>(len) * (s + 1) / 8);
+  return w0 + (x - x0) * (w1 - w0) / (x1 > x0 ? x1 - x0 : 1);
+}
+// first column of a row's 32-column band (raven_amd/csrc/poa4.hip poa4_band_start): centre - 16, clamped to
+// [0, len + 1 - 32], even (rounded up at the right limit so that the band keeps the last column)
+static std::int32_t BandStart32(std::int32_t len, std::int32_t x, std::int32_t span) {
+  std::int32_t b = StraightCentre(len, x, span) - 16;
+  const std::int32_t bmax = len + 1 - 32;
+  b = b > bmax ? bmax : b;
+  b = b < 0 ? 0 : b;
+  return (b == bmax && bmax > 0) ? (b + 1) & ~1 : b & ~1;
+}
+
 bool BuildWindowGraph(const std::vector<Layer>& layers, std::int8_t m, std::int8_t n, std::int8_t g, bool device_order,
-                      Graph* out, int where = 3) {
+                      Graph* out, int where = 3, std::vector<LayerStats>* stats = nullptr) {
   const Layer& bb = layers.front();
+  std::vector<std::uint32_t> bpos(bb.len);  // the kernels' backbone coordinate of a node (carried over insertions)
+  for (std::uint32_t i = 0; i < bb.len; ++i) bpos[i] = i;
+  if (stats) stats->assign(layers.size(), LayerStats());
   Graph& graph = *out;
   graph = Graph();
   graph.AddAlignment(Alignment(), bb.codes, bb.len, Weights(bb));
@@ -481,17 +523,92 @@ bool BuildWindowGraph(const std::vector<Layer>& layers, std::int8_t m, std::int8
   for (std::uint32_t j = 1; j < layers.size(); ++j) {
     const Layer& l = layers[rank[j]];
     Alignment alignment;
-    if (l.begin < offset && l.end > bb.len - offset) {
+    std::vector<std::uint32_t> mapping;
+    const bool full = l.begin < offset && l.end > bb.len - offset;
+    if (full) {
       alignment = AlignNW(l.codes, l.len, graph, m, n, g);
     } else {
-      std::vector<std::uint32_t> mapping;
       auto subgraph = graph.Subgraph(l.begin, l.end, &mapping, in_alignment ? &node_rank : nullptr);
       alignment = AlignNW(l.codes, l.len, subgraph, m, n, g);
       for (auto& it : alignment)
         if (it.first != -1) it.first = mapping[it.first];
     }
     const std::uint32_t n_old = graph.nodes.size();
+    if (stats && device_order && l.len) {
+      LayerStats& s = (*stats)[rank[j]];
+      const std::int32_t len = l.len, lb = l.begin, span = static_cast<std::int32_t>(l.end) - lb + 1;
+      std::vector<char> in(n_old, full ? 1 : 0);
+      for (auto v : mapping) in[v] = 1;
+      std::uint32_t r_lo = n_old, r_hi = 0;
+      for (std::uint32_t v = 0; v < n_old; ++v)
+        if (in[v]) {
+          r_lo = std::min(r_lo, node_rank[v]);
+          r_hi = std::max(r_hi, node_rank[v] + 1);
+        }
+      s.nodes = n_old;
+      s.rows = r_hi > r_lo ? r_hi - r_lo : 0;
+      bool any = false;
+      std::int32_t busiest = -1;
+      std::vector<std::uint32_t> by_rank(n_old);
+      for (std::uint32_t v = 0; v < n_old; ++v) by_rank[node_rank[v]] = v;
+      for (std::uint32_t v : by_rank) {
+        if (!in[v]) continue;
+        std::int64_t deg = 0, long_here = -1;
+        for (auto e : graph.nodes[v].inedges) {
+          const std::uint32_t t = graph.edges[e].tail;
+          if (!in[t]) {
+            if (node_rank[t] < r_lo) ++s.tails_below;
+            continue;
+          }
+          if (static_cast<std::int64_t>(node_rank[v]) - node_rank[t] > s.in_edge_ranks) {
+            s.in_edge_ranks = static_cast<std::int64_t>(node_rank[v]) - node_rank[t];
+            s.long_index = long_here = deg;
+          }
+          ++deg;
+          const std::int64_t d = BandStart32(len, static_cast<std::int32_t>(bpos[v]) - lb, span) -
+                                 BandStart32(len, static_cast<std::int32_t>(bpos[t]) - lb, span);
+          s.band_step = any ? std::max(s.band_step, d) : d;
+          s.band_step_min = any ? std::min(s.band_step_min, d) : d;
+          any = true;
+        }
+        if (deg > s.in_degree) {
+          s.in_degree = deg;
+          busiest = static_cast<std::int32_t>(v);
+        }
+        if (long_here >= 0) s.long_degree = deg;
+      }
+      std::int32_t pos = 0, node = -1;
+      for (const auto& it : alignment) {
+        if (it.second != -1) pos = it.second;
+        if (it.first != -1 && it.first == busiest && node >= 0) {
+          std::int64_t k = 0;
+          for (auto e : graph.nodes[busiest].inedges) {
+            const std::uint32_t t = graph.edges[e].tail;
+            if (!in[t]) continue;
+            if (static_cast<std::int32_t>(t) == node) {
+              s.walk_index = k;
+              s.walk_vertical = it.second == -1 ? 1 : 0;
+            }
+            ++k;
+          }
+        }
+        if (it.first != -1) node = it.first;
+        if (node < 0) continue;
+        const std::int64_t c = StraightCentre(len, static_cast<std::int32_t>(bpos[node]) - lb, span);
+        s.off_centre = std::max<std::int64_t>(s.off_centre, pos > c ? pos - c : c - pos);
+      }
+    }
     graph.AddAlignment(alignment, l.codes, l.len, Weights(l));
+    {  // backbone coordinates of the new nodes, as the kernels assign them
+      bpos.resize(graph.nodes.size(), 0);
+      std::uint32_t carry = l.begin;
+      for (std::size_t q = 0; q < graph.path_nodes.size(); ++q)
+        if (graph.path_aligned[q] != -1) { carry = bpos[graph.path_aligned[q]]; break; }
+      for (std::size_t q = 0; q < graph.path_nodes.size(); ++q) {
+        if (graph.path_aligned[q] != -1) carry = bpos[graph.path_aligned[q]];
+        if (static_cast<std::uint32_t>(graph.path_nodes[q]) >= n_old) bpos[graph.path_nodes[q]] = carry;
+      }
+    }
     if (device_order) {
       if (!DeviceOrderUpdate(graph, n_old, &node_rank)) {
         return false;
@@ -582,6 +699,58 @@ int orc_poa_window(const std::uint8_t* codes, const std::uint8_t* quals, const s
   *out_len = cons.size();
   std::memcpy(out, cons.data(), std::min<std::size_t>(cons.size(), out_cap));
   return polished ? 1 : 0;
+}
+
+// The graph a window's layers meet, under the statement of what the device kernels compute (the device's row order, end
+// node by smallest node id): per layer (in the caller's order; the backbone's row stays 0) twelve values —
+// nodes, largest in-degree, longest in-edge in ranks, tails below the rank range, largest distance of the alignment path
+// from the straight band centre, largest and smallest 32-column band-start difference along an in-edge, ranks in the
+// subgraph's range, the longest in-edge's place among its head's in-edges, that head's in-degree, the in-edge through which the layer's path enters the row of the largest in-degree and whether it
+// passes that row vertically — and for the window: whole[0] = final node count, whole[1] = 1 if that statement and spoa's own rules
+// give the same consensus bytes with the coverage trim on and off, whole[2] = largest in-degree of the final graph.
+// Returns 0, -1 for invalid layer positions, -2 if the device's order rule broke down.
+int orc_poa_window_stats(const std::uint8_t* codes, const std::uint8_t* quals, const std::uint64_t* offsets,
+                         const std::uint32_t* begins, const std::uint32_t* ends, std::uint32_t n_layers, int m, int n, int g,
+                         std::int64_t* per_layer, std::int64_t* whole) {
+  std::vector<poa::Layer> layers(n_layers);
+  for (std::uint32_t i = 0; i < n_layers; ++i) {
+    layers[i].codes = codes + offsets[i];
+    layers[i].qual = quals ? quals + offsets[i] : nullptr;
+    layers[i].len = static_cast<std::uint32_t>(offsets[i + 1] - offsets[i]);
+    layers[i].begin = begins[i];
+    layers[i].end = ends[i];
+  }
+  for (std::uint32_t i = 1; i < n_layers; ++i)
+    if (layers[i].len && (begins[i] >= ends[i] || ends[i] >= layers[0].len)) return -1;
+  const int tie0 = poa::g_end_tie_rule, where0 = poa::g_order_where;
+  poa::g_order_where = 3;
+  poa::g_end_tie_rule = 1;
+  poa::Graph graph;
+  std::vector<poa::LayerStats> stats;
+  const bool ok = poa::BuildWindowGraph(layers, m, n, g, true, &graph, 3, &stats);
+  bool agree = ok;
+  for (int trim = 0; trim < 2 && agree; ++trim) {
+    std::vector<std::uint8_t> a, b;
+    poa::g_end_tie_rule = 1;
+    poa::WindowConsensus(layers, m, n, g, trim != 0, &a, nullptr, true);
+    poa::g_end_tie_rule = 0;
+    poa::WindowConsensus(layers, m, n, g, trim != 0, &b, nullptr, false);
+    agree = a == b;
+  }
+  poa::g_end_tie_rule = tie0;
+  poa::g_order_where = where0;
+  if (!ok) return -2;
+  for (std::uint32_t i = 0; i < n_layers; ++i) {
+    const poa::LayerStats& s = stats[i];
+    const std::int64_t v[12] = {s.nodes,     s.in_degree,     s.in_edge_ranks, s.tails_below, s.off_centre, s.band_step,
+                                s.band_step_min, s.rows,      s.long_index,    s.long_degree, s.walk_index, s.walk_vertical};
+    std::memcpy(per_layer + 12 * static_cast<std::size_t>(i), v, sizeof(v));
+  }
+  whole[0] = graph.nodes.size();
+  whole[1] = agree ? 1 : 0;
+  whole[2] = 0;
+  for (const auto& nd : graph.nodes) whole[2] = std::max<std::int64_t>(whole[2], nd.inedges.size());
+  return 0;
 }
 
 // DEBUG: replays the device kernel's incremental topological-order rule (raven_amd/csrc/poa.hip step 5) next to
