@@ -582,6 +582,30 @@ int rvn_group_filter_overlaps_by_identity(rvn_group* g, const uint64_t* packed, 
 int rvn_overlap_update_and_type(rvn_overlap* overlaps, uint64_t n, const uint32_t* pile_begin, const uint32_t* pile_end,
                                 const uint8_t* pile_invalid, uint32_t n_piles, uint8_t* ok, uint32_t* type);
 
+/* The force-directed layout of raven's RemoveLongEdges (RavenLib/src/assemble.cc:357-627: a Barnes-Hut quadtree and one
+ * force per point, n_iterations times) for every component of the call at once, bit for bit what the reference's loop
+ * computes from the same start positions.  Points [component_offsets[c], component_offsets[c + 1]) are
+ * component c; xy_in holds their start positions (x, y per point: the reference draws them from its generator, the
+ * facade include/raven_hip/layout.hpp does the same); adj[adj_offsets[i] .. adj_offsets[i + 1]) are the neighbours of
+ * point i as point indices, in the order their attraction terms are added (the reference: in-edges, out-edges,
+ * transitive).  Per component k = sqrt(1 / size), t = 0.1, dt = t / (n_iterations + 1), t -= dt after every iteration.
+ * xy_out receives the positions after the last iteration (n_iterations == 0: xy_in).  Components of any size are taken:
+ * the reference's size >= 6 and junction rules are the caller's.
+ * stats (may be NULL): host_tree_iterations = (component, iteration) pairs whose repulsive forces were computed on the
+ * host from an insertion-built tree, because two points shared a 32-level path or a point fell between the children of
+ * a cell (the only cases in which the reference's tree depends on its insertion order); max_depth = the deepest tree
+ * built on the device.
+ * RVN_EINVAL: offsets that do not ascend from 0, an empty component, a neighbour outside its point's component, a
+ * coordinate that is NaN or infinite, more than 2^28 points. */
+typedef struct {
+  uint64_t host_tree_iterations;
+  uint32_t max_depth;
+  uint32_t reserved;
+} rvn_layout_stats;
+int rvn_layout_force_directed(rvn_engine* e, uint32_t n_components, const uint32_t* component_offsets, const double* xy_in,
+                              const uint64_t* adj_offsets, const uint32_t* adj, uint32_t n_iterations, double* xy_out,
+                              rvn_layout_stats* stats);
+
 /* Tuning a deployment may set; -1 restores the built-in default of any option (so does 0, except for poa_rows_min_windows).
  * No option changes an overlap list, a pile or a layer table; poa_rows_min_windows chooses which window-consensus kernel
  * makes the first attempt, and the two agree on 19 998 of 20 000 C4-like windows, not on every one: a

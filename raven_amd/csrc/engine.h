@@ -520,6 +520,17 @@ void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32
                                      const u8* h_kmers, const u64* h_kmer_off, const u32* h_begin, const u32* h_end,
                                      const u16* h_median, const u8* h_invalid, RepeatResult& res);
 
+// The force-directed layout of raven's RemoveLongEdges (layout.hip; arithmetic: layout.h): every component of the call
+// (points [off[c], off[c + 1])) laid out for n_iterations from the given start positions; neighbours are point indices
+// in the order their terms are added.  host_tree_iterations counts the (component, iteration) pairs whose repulsive
+// forces came from the host's insertion-built tree, max_depth is the deepest device tree of the call.
+struct LayoutStats {
+  u64 host_tree_iterations = 0;
+  u32 max_depth = 0;
+};
+void layout_force_directed(Engine& e, u32 n_components, const u32* h_off, const double* h_xy, const u64* h_adj_off,
+                           const u32* h_adj, u32 n_iterations, double* h_xy_out, LayoutStats& st);
+
 }  // namespace rvn
 
 // Handles of the C ABI (include/raven_hip.h) that several translation units look into

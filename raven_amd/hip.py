@@ -145,6 +145,7 @@ _SIGNATURES = {
                                                               _dbl, _u64, _pp]),
     "rvn_group_filter_overlaps_by_identity": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _dbl]),
     "rvn_overlap_update_and_type": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "rvn_layout_force_directed": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
     "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
     "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
@@ -910,6 +911,23 @@ class Engine:
                                                      _p(np.ascontiguousarray(pile_end, dtype=np.uint32)),
                                                      _p(np.ascontiguousarray(pile_invalid, dtype=np.uint8)), float(identity)))
         return o[:int(off[-1])], off
+
+    def layout_force_directed(self, component_offsets, xy, adj_offsets, adj, n_iterations=100):
+        """raven's force-directed layout of every component at once (rvn_layout_force_directed): xy float64[n, 2] start
+        positions, adj the neighbours of each point as point indices (CSR, in the order their terms are added).
+        Returns (float64[n, 2] positions after the last iteration, {"host_tree_iterations", "max_depth"})."""
+        off = np.ascontiguousarray(component_offsets, dtype=np.uint32)
+        pos = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        aoff = np.ascontiguousarray(adj_offsets, dtype=np.uint64)
+        a = np.ascontiguousarray(adj, dtype=np.uint32)
+        if off.shape[0] < 1 or pos.shape[0] != int(off[-1]) or aoff.shape[0] != pos.shape[0] + 1 or (
+                aoff.shape[0] and a.shape[0] < int(aoff[-1])):
+            raise ValueError("layout_force_directed: array sizes do not fit the offsets")
+        out = np.zeros_like(pos)
+        st = np.zeros(2, dtype=np.uint64)  # rvn_layout_stats: uint64, uint32, uint32
+        _check(lib().rvn_layout_force_directed(self._h, off.shape[0] - 1, _p(off), _p(pos), _p(aoff), _p(a), int(n_iterations),
+                                               _p(out), _p(st)))
+        return out, {"host_tree_iterations": int(st[0]), "max_depth": int(st[1] & 0xFFFFFFFF)}
 
     def release_scratch(self):
         _check(lib().rvn_engine_release_scratch(self._h))
