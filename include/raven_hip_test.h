@@ -128,6 +128,13 @@ int rvn_test_radix_sort_pairs(int variant, uint64_t* keys, uint64_t* values, uin
  * (device 0), one call, no kernel launched from here. */
 int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_t in_offset_items,
                             uint32_t out_offset_items, uint64_t* out);
+/* compact_overlap_list (pass2.hip), the overlap phase's keep flags -> survivors in order, on n host overlaps: applied
+ * with keep1[n] (flags 0 or 1), then, when keep2 is not NULL, again with keep2[kept1] on the same three buffers, so that
+ * list and spare change places in both directions.  out[n] takes the survivors, *n_out their number, slot[n + 1] the scan
+ * the last application left: slot[0 .. m] for its m flags, slot[m] = their sum (an application to an empty list scans
+ * nothing: slot[0] = 0).  Engine of its own (device 0), no kernel launched from here. */
+int rvn_test_compact_overlap_list(const rvn_overlap* in, uint64_t n, const uint8_t* keep1, const uint8_t* keep2,
+                                  rvn_overlap* out, uint64_t* n_out, uint32_t* slot);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

@@ -88,4 +88,18 @@ inline void put(Engine& e, void* dst, const void* src, size_t bytes, hipMemcpyKi
   else RVN_HIP(hipMemcpy(dst, src, bytes, kind));
 }
 
+// The argument check of a CSR offsets array off[n + 1] whose lists must stay below max_len entries: nullptr, or what is
+// wrong with it (the entry point puts its name in front).
+constexpr u64 kMaxPileCells = 1ULL << 27;  // a pile's coverage / k-mer cells
+constexpr u64 kNoCsrLimit = ~0ULL;
+template <typename T>
+const char* csr_offsets_error(const T* off, u32 n, u64 max_len) {
+  if (off[0] != 0) return "offsets must start at 0";
+  for (u32 i = 0; i < n; ++i) {
+    if (off[i + 1] < off[i]) return "offsets must not decrease";
+    if (off[i + 1] - off[i] >= max_len) return "a pile of 2^27 cells or more";
+  }
+  return nullptr;
+}
+
 }  // namespace rvn

@@ -99,10 +99,8 @@ int rvn_shard_sketch_range(rvn_engine* h, const rvn_reads* rr, uint32_t first, u
           n_acc += n;
         }
         RVN_HIP(rvn_stream_sync(e.stream));
-        std::swap(e.index_sketch.val.ptr, e.foreign_val.ptr);
-        std::swap(e.index_sketch.val.cap, e.foreign_val.cap);
-        std::swap(e.index_sketch.org.ptr, e.foreign_org.ptr);
-        std::swap(e.index_sketch.org.cap, e.foreign_org.cap);
+        e.index_sketch.val.swap(e.foreign_val);
+        e.index_sketch.org.swap(e.foreign_org);
         e.index_sketch.first = first;
         e.index_sketch.last = last;
         e.index_sketch.count = n_acc;  // (read_off of the pieces is not kept: nothing downstream of a query-only sketch reads it)

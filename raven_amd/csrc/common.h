@@ -121,6 +121,18 @@ struct DevBuf {
     reserve(count * sizeof(T));
     return reinterpret_cast<T*>(ptr);
   }
+  // the two buffers change owners: pointer AND capacity (a capacity left behind frees the wrong block at the next reserve)
+  void swap(DevBuf& o) {
+    void* const p = ptr;
+    const size_t c = cap;
+    ptr = o.ptr;
+    cap = o.cap;
+    o.ptr = p;
+    o.cap = c;
+  }
+  // Grow-preserving device append: room for need_bytes with the first used_bytes kept.  A buffer that has to grow
+  // becomes one of twice the need (1 MB at least); the stream is synchronised before the old block goes back.
+  void grow_keeping(size_t used_bytes, size_t need_bytes, hipStream_t s);
 };
 
 // Growable pinned host buffer (device -> host read-backs of bulk results at PCIe speed, no page-fault zeroing).
@@ -192,6 +204,15 @@ inline hipError_t rvn_stream_sync(hipStream_t s) {
     if (q != hipErrorNotReady) return q;
     if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) return hipStreamSynchronize(s);
   }
+}
+
+inline void DevBuf::grow_keeping(size_t used_bytes, size_t need_bytes, hipStream_t s) {
+  if (need_bytes <= cap) return;
+  DevBuf bigger;
+  bigger.reserve(std::max<size_t>(need_bytes * 2, 1 << 20));
+  if (used_bytes) RVN_HIP(hipMemcpyAsync(bigger.ptr, ptr, used_bytes, hipMemcpyDeviceToDevice, s));
+  RVN_HIP(rvn_stream_sync(s));
+  swap(bigger);
 }
 
 struct KernelTimers {

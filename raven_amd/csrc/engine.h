@@ -440,11 +440,36 @@ void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u
                            const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd);
 void identity_filter_compact(Overlap* h_ovl, u32* h_off, u32 n, const u8* ok, const Overlap* upd);
 // OverlapUpdate + [identity != 0: the edit-distance score] on a list in HBM, in place: ok flags out.  regions by read id,
-// index_of: id -> index in r (both unused when identity == 0, where this is update_kernel alone)
+// index_of: id -> index in r, nullptr = the ids are the indices (both unused when identity == 0, where this is
+// update_kernel alone)
 void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, const PileRegion* d_regions,
                          const u32* d_index_of, double identity, u8* d_ok);
-// compact_kernel: out[slot[i]] = in[i] where keep[i]
+
+// ---- keep flags -> survivors, in order (pass2.hip).  The flags are 0 or 1 by contract: the scan sums them. ----
+// slot (u32[n + 1]) = exclusive scan of keep[0..n), slot[n] = the number kept, which is read back (one stream sync).
+// n == 0: no launch, nothing kept.
+struct KeptSlots {
+  const u32* slot;
+  u64 kept;
+};
+KeptSlots kept_slots(Engine& e, const u8* d_keep, u64 n, DevBuf& slot);
+// compact_kernel, the one scatter launch: out[slot[i]] = in[i] where keep[i]
 void compact_overlaps(Engine& e, const Overlap* d_in, const u8* d_keep, const u32* d_slot, u64 n, Overlap* d_out);
+// list[0..n) becomes its survivors: kept_slots, the scatter into spare, list.swap(spare).  Returns the number kept; slot
+// stays valid for the caller.  No stream sync behind the scatter: spare, which now holds the old list, is regrown only
+// behind the read-back of the next call, and every caller ends its stage on a sync of its own before the buffers are
+// used for anything else.
+u64 compact_overlap_list(Engine& e, DevBuf& list, u64 n, const u8* d_keep, DevBuf& slot, DevBuf& spare);
+
+// Host array -> device buffer on the stream (asynchronous: the host array outlives the copy); nothing copied at count == 0
+template <typename T>
+T* upload(DevBuf& b, const T* h, size_t count, hipStream_t s) {
+  T* d = b.get<T>(count + 16);
+  if (count) RVN_HIP(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, s));
+  return d;
+}
+// PileRegion{begin, end, invalid ? 1 : 0} of n piles into b, positions in bases (pass2.hip); synchronises the stream
+PileRegion* upload_pile_regions(Engine& e, DevBuf& b, const u32* h_begin, const u32* h_end, const u8* h_invalid, u32 n);
 
 // ResolveContainedReads / ResolveChimericSequences on the device (resolve.hip): the piles' state and the per-pile
 // overlap lists in HBM between and after the two phases

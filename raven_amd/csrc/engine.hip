@@ -17,11 +17,6 @@ const char* kStageNames[StageTimes::kNum] = {"sketch", "sort", "index", "filter"
                                              "seg_sort", "intervals", "chain", "compact", "merge", "pile",
                                              "truncate"};
 
-void swap_bufs(DevBuf& a, DevBuf& b) {
-  std::swap(a.ptr, b.ptr);
-  std::swap(a.cap, b.cap);
-}
-
 }  // namespace
 
 namespace rvn {
@@ -57,9 +52,9 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
       sketch_minhash(e, r, e.raw_sketch, is);
       ix.all_query = true;
     } else if (!minhash) {
-      swap_bufs(is.val, e.raw_sketch.val);
-      swap_bufs(is.org, e.raw_sketch.org);
-      swap_bufs(is.read_off, e.raw_sketch.read_off);
+      is.val.swap(e.raw_sketch.val);
+      is.org.swap(e.raw_sketch.org);
+      is.read_off.swap(e.raw_sketch.read_off);
       is.first = first;
       is.last = last;
       is.count = e.raw_sketch.count;
@@ -90,8 +85,8 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
   // sketch, so that TWO sets circulate (raw sketch <-> index side 0) and the second pass already finds its buffers —
   // left alone, three sets rotate through the three owners and every one of them is grown once (0.5 s at C4).
   if (raw_handed_over) {
-    if (e.raw_sketch.val.cap < e.index_sketch.val.cap) swap_bufs(e.raw_sketch.val, e.index_sketch.val);
-    if (e.raw_sketch.org.cap < e.index_sketch.org.cap) swap_bufs(e.raw_sketch.org, e.index_sketch.org);
+    if (e.raw_sketch.val.cap < e.index_sketch.val.cap) e.raw_sketch.val.swap(e.index_sketch.val);
+    if (e.raw_sketch.org.cap < e.index_sketch.org.cap) e.raw_sketch.org.swap(e.index_sketch.org);
   }
 }
 

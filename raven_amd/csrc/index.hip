@@ -224,10 +224,8 @@ void index_build_impl(Engine& e, Sketch& sk, bool build_table) {
   if (m >= (1ULL << 32)) throw HipError("[raven_hip] index batch with >= 2^32 minimizers is not supported");
 
   // adopt the sketch buffers as ping side 0 (swap ownership, no copy)
-  std::swap(ix.s_val[0].ptr, sk.val.ptr);
-  std::swap(ix.s_val[0].cap, sk.val.cap);
-  std::swap(ix.s_org[0].ptr, sk.org.ptr);
-  std::swap(ix.s_org[0].cap, sk.org.cap);
+  ix.s_val[0].swap(sk.val);
+  ix.s_org[0].swap(sk.org);
   ix.cur = 0;
   if (m == 0) {
     ix.table_bits = 1;

@@ -89,17 +89,6 @@ __global__ void block_quality_kernel(const u8* __restrict__ quals, const u64* __
   out[bi] = static_cast<u8>((cnt ? sum / cnt : 0u) + 33u);
 }
 
-// grow-preserving device append
-void ensure_capacity(DevBuf& buf, u64 used_bytes, u64 need_bytes, hipStream_t s) {
-  if (need_bytes <= buf.cap) return;
-  DevBuf bigger;
-  bigger.reserve(std::max<u64>(need_bytes * 2, 1 << 20));
-  if (used_bytes) RVN_HIP(hipMemcpyAsync(bigger.ptr, buf.ptr, used_bytes, hipMemcpyDeviceToDevice, s));
-  RVN_HIP(rvn_stream_sync(s));
-  std::swap(buf.ptr, bigger.ptr);
-  std::swap(buf.cap, bigger.cap);
-}
-
 bool has_suffix(const std::string& s, const char* suf) {
   const size_t n = std::strlen(suf);
   return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
@@ -190,7 +179,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
       RVN_HIP(hipMemcpyAsync(dfo, foff.data(), nr * 8ULL, hipMemcpyHostToDevice, s));
       RVN_HIP(hipMemcpyAsync(dln, lens.data(), nr * 4ULL, hipMemcpyHostToDevice, s));
       RVN_HIP(hipMemcpyAsync(dwo, woff.data(), (nr + 1) * 8ULL, hipMemcpyHostToDevice, s));
-      ensure_capacity(R.packed, words_used * 8, (words_used + nw + 2) * 8, s);
+      R.packed.grow_keeping(words_used * 8, (words_used + nw + 2) * 8, s);
       if (nw) {
         pack_ascii_kernel<<<div_up(nw, 256), 256, 0, s>>>(text, dfo, dln, dwo, nr, nw, R.packed.as<u64>() + words_used, d_bad);
         RVN_LAUNCH_CHECK();
@@ -200,7 +189,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
         u64* dqo = d_qoff.get<u64>(nr + 1);
         RVN_HIP(hipMemcpyAsync(dqf, qfoff.data(), nr * 8ULL, hipMemcpyHostToDevice, s));
         RVN_HIP(hipMemcpyAsync(dqo, qoff.data(), (nr + 1) * 8ULL, hipMemcpyHostToDevice, s));
-        ensure_capacity(R.quals, qblocks_used, qblocks_used + nq + 16, s);
+        R.quals.grow_keeping(qblocks_used, qblocks_used + nq + 16, s);
         if (nq) {
           block_quality_kernel<<<div_up(nq, 256), 256, 0, s>>>(text, dqf, dln, dqo, nr, nq, R.quals.as<u8>() + qblocks_used);
           RVN_LAUNCH_CHECK();
@@ -255,7 +244,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
     scan_busy += secs(t0);
     const auto t1 = std::chrono::steady_clock::now();
     if (run_base < text_base) throw std::logic_error("[raven_hip] input path: run before the retained text");
-    ensure_capacity(e.io_text[cur], run_base - text_base, run_base - text_base + run_len + 64, s);
+    e.io_text[cur].grow_keeping(run_base - text_base, run_base - text_base + run_len + 64, s);
     if (run_len)
       RVN_HIP(hipMemcpyAsync(e.io_text[cur].as<u8>() + (run_base - text_base), run, run_len, hipMemcpyHostToDevice, s));
     RVN_HIP(hipEventRecord(ev[k & 1], s));
@@ -271,7 +260,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
     u8 extra = 0;
     const u64 at = scanner.text_end();
     if (scanner.finish(recs, rec_names, &extra)) {
-      ensure_capacity(e.io_text[cur], at - text_base, at - text_base + 64, s);
+      e.io_text[cur].grow_keeping(at - text_base, at - text_base + 64, s);
       RVN_HIP(hipMemcpy(e.io_text[cur].as<u8>() + (at - text_base), &extra, 1, hipMemcpyHostToDevice));
     }
     const auto t1 = std::chrono::steady_clock::now();
@@ -288,7 +277,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
   R.h_id.resize(nseq);
   for (u32 i = 0; i < nseq; ++i) R.h_id[i] = i;
   R.ids_are_indices = true;
-  ensure_capacity(R.packed, words_used * 8, (words_used + 2) * 8, s);
+  R.packed.grow_keeping(words_used * 8, (words_used + 2) * 8, s);
   RVN_HIP(hipMemsetAsync(R.packed.as<u64>() + words_used, 0, 16, s));
   u64* d_wo = R.word_off.get<u64>(static_cast<size_t>(nseq) + 1);
   u32* d_ln = R.len.get<u32>(static_cast<size_t>(nseq) + 1);

@@ -96,7 +96,8 @@ __global__ void ed_pairs_kernel(const Overlap* __restrict__ ovl, const u8* __res
   if (i >= n || !ok[i]) return;
   const Overlap o = ovl[i];
   const u32 a = o.lhs_end - o.lhs_begin, b = o.rhs_end - o.rhs_begin;
-  pairs[slot[i]] = EdPairRec{index_of[o.lhs_id], o.lhs_begin, a, index_of[o.rhs_id], o.rhs_begin, b, o.strand ? 1u : 0u, 0u};
+  const u32 ai = index_of ? index_of[o.lhs_id] : o.lhs_id, bi = index_of ? index_of[o.rhs_id] : o.rhs_id;
+  pairs[slot[i]] = EdPairRec{ai, o.lhs_begin, a, bi, o.rhs_begin, b, o.strand ? 1u : 0u, 0u};
   const u32 maxlen = a > b ? a : b;
   double guess = (1. - identity) * static_cast<double>(maxlen);
   guess = guess < 0 ? 0 : (guess > static_cast<double>(maxlen) ? static_cast<double>(maxlen) : guess);
@@ -174,23 +175,14 @@ __global__ void merge_invalid_kernel(PileRegion* __restrict__ regions, const u8*
   if (i < n && contained[i]) regions[i].invalid = 1;
 }
 
-// keep flags -> compacted list (in place through a temporary); returns the new count
-u64 compact(Engine& e, DevBuf& list, u64 n, const u8* d_keep, DevBuf& tmp_slot, DevBuf& tmp_out) {
-  if (n == 0) return 0;
-  hipStream_t s = e.stream;
-  u32* d_slot = tmp_slot.get<u32>(n + 2);
-  exclusive_scan_u8_u32(d_keep, d_slot, n, e.scan_tmp, s);
-  const u64 m = read_back(e, d_slot + n, 4);
-  Overlap* d_out = tmp_out.get<Overlap>(m + 1);
-  compact_kernel<<<div_up(n, 256), 256, 0, s>>>(list.as<Overlap>(), d_keep, d_slot, n, d_out);
-  RVN_LAUNCH_CHECK();
-  RVN_HIP(rvn_stream_sync(s));
-  std::swap(list.ptr, tmp_out.ptr);
-  std::swap(list.cap, tmp_out.cap);
-  return m;
-}
-
 }  // namespace
+
+KeptSlots kept_slots(Engine& e, const u8* d_keep, u64 n, DevBuf& slot) {
+  if (n == 0) return {nullptr, 0};
+  u32* d_slot = slot.get<u32>(n + 2);
+  exclusive_scan_u8_u32(d_keep, d_slot, n, e.scan_tmp, e.stream);
+  return {d_slot, read_back(e, d_slot + n, 4)};
+}
 
 void compact_overlaps(Engine& e, const Overlap* d_in, const u8* d_keep, const u32* d_slot, u64 n, Overlap* d_out) {
   if (n == 0) return;
@@ -198,7 +190,16 @@ void compact_overlaps(Engine& e, const Overlap* d_in, const u8* d_keep, const u3
   RVN_LAUNCH_CHECK();
 }
 
-// OverlapUpdate + [identity] on a device list; ok flags out.  regions indexed by read id, index_of: id -> index in r.
+u64 compact_overlap_list(Engine& e, DevBuf& list, u64 n, const u8* d_keep, DevBuf& slot, DevBuf& spare) {
+  if (n == 0) return 0;
+  const KeptSlots ks = kept_slots(e, d_keep, n, slot);
+  compact_overlaps(e, list.as<Overlap>(), d_keep, ks.slot, n, spare.get<Overlap>(ks.kept + 1));
+  list.swap(spare);
+  return ks.kept;
+}
+
+// OverlapUpdate + [identity] on a device list; ok flags out.  regions indexed by read id, index_of: id -> index in r
+// (nullptr: the ids are the indices).
 void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, const PileRegion* d_regions,
                          const u32* d_index_of, double identity, u8* d_ok) {
   if (n == 0) return;
@@ -206,9 +207,9 @@ void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, co
   update_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, n, d_regions, d_ok);
   RVN_LAUNCH_CHECK();
   if (identity == 0) return;
-  u32* d_slot = e.p2_slot.get<u32>(n + 2);
-  exclusive_scan_u8_u32(d_ok, d_slot, n, e.scan_tmp, s);
-  const u64 np = read_back(e, d_slot + n, 4);
+  const KeptSlots ks = kept_slots(e, d_ok, n, e.p2_slot);
+  const u32* d_slot = ks.slot;
+  const u64 np = ks.kept;
   if (np == 0) return;
   if (np >= 0xFFFFFFFFULL) throw std::invalid_argument("[raven_hip] identity filter: too many pairs in one batch");
   EdPairRec* d_pairs = e.p2_pairs.get<EdPairRec>(np + 1);
@@ -221,18 +222,13 @@ void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, co
   RVN_LAUNCH_CHECK();
 }
 
-namespace {
-
-PileRegion* upload_regions(Engine& e, const u32* h_begin, const u32* h_end, const u8* h_invalid, u32 n) {
+PileRegion* upload_pile_regions(Engine& e, DevBuf& b, const u32* h_begin, const u32* h_end, const u8* h_invalid, u32 n) {
   std::vector<PileRegion> reg(n);
   for (u32 i = 0; i < n; ++i) reg[i] = PileRegion{h_begin[i], h_end[i], h_invalid[i] ? 1u : 0u};
-  PileRegion* d = e.p2_regions.get<PileRegion>(static_cast<size_t>(n) + 1);
-  RVN_HIP(hipMemcpyAsync(d, reg.data(), static_cast<size_t>(n) * sizeof(PileRegion), hipMemcpyHostToDevice, e.stream));
-  RVN_HIP(rvn_stream_sync(e.stream));
+  PileRegion* d = upload(b, reg.data(), n, e.stream);
+  RVN_HIP(rvn_stream_sync(e.stream));  // reg is gone on return
   return d;
 }
-
-}  // namespace
 
 // Device copy of the reads `src` (indices into R, increasing) as a read set of its own: ids = the original indices
 void reads_subset(Engine& e, const ReadsDev& R, const std::vector<u32>& src, ReadsDev& V) {
@@ -298,7 +294,7 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
   out.n = n;
   out.n_overlaps = 0;
   P.batches.clear();
-  P.d_regions = upload_regions(e, h_begin, h_end, h_invalid, n);
+  P.d_regions = upload_pile_regions(e, e.p2_regions, h_begin, h_end, h_invalid, n);
   u8* d_contained = out.contained.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemsetAsync(d_contained, 0, static_cast<size_t>(n) + 16, s));
   // valid reads first, by id (construct.cc:324-349); index_of: id -> position among the valid reads
@@ -333,10 +329,8 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
   }
   const u32 sv = P.sv;
   reads_subset(e, R, P.valid, P.V);
-  P.d_index_of = e.p2_index_of.get<u32>(static_cast<size_t>(n) + 1);
-  RVN_HIP(hipMemcpyAsync(P.d_index_of, index_of.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
-  P.d_v_kmers_off = e.p2_kmers_off.get<u64>(static_cast<size_t>(sv) + 1);
-  RVN_HIP(hipMemcpyAsync(P.d_v_kmers_off, P.h_v_kmers_off.data(), (static_cast<size_t>(sv) + 1) * 8, hipMemcpyHostToDevice, s));
+  P.d_index_of = upload(e.p2_index_of, index_of.data(), n, s);
+  P.d_v_kmers_off = upload(e.p2_kmers_off, P.h_v_kmers_off.data(), static_cast<size_t>(sv) + 1, s);
   RVN_HIP(rvn_stream_sync(s));
   // index batches of batch_bases valid bases: [first, last) of the valid reads
   u64 bytes = 0;
@@ -378,21 +372,12 @@ u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first,
   update_and_identity(e, V, d_ovl, O, P.d_regions, P.d_index_of, identity, d_ok);
   classify_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_ok, O, P.d_regions, out.contained.as<u8>(), d_keep);
   RVN_LAUNCH_CHECK();
-  u32* d_slot = e.p2_slot.get<u32>(O + 2);
-  exclusive_scan_u8_u32(d_keep, d_slot, O, e.scan_tmp, s);
-  const u64 m = read_back(e, d_slot + O, 4);
+  const KeptSlots ks = kept_slots(e, d_keep, O, e.p2_slot);
+  const u64 m = ks.kept;
   if (m == 0) return 0;
-  // append to the result list (grow-preserving)
-  if ((acc_n + m + 1) * sizeof(Overlap) > out.ovl.cap) {
-    DevBuf bigger;
-    bigger.reserve((acc_n + m + 1) * sizeof(Overlap) * 2);
-    if (acc_n) RVN_HIP(hipMemcpyAsync(bigger.ptr, out.ovl.ptr, acc_n * sizeof(Overlap), hipMemcpyDeviceToDevice, s));
-    RVN_HIP(rvn_stream_sync(s));
-    std::swap(out.ovl.ptr, bigger.ptr);
-    std::swap(out.ovl.cap, bigger.cap);
-  }
-  compact_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_keep, d_slot, O, out.ovl.as<Overlap>() + acc_n);
-  RVN_LAUNCH_CHECK();
+  // append to the result list
+  out.ovl.grow_keeping(acc_n * sizeof(Overlap), (acc_n + m + 1) * sizeof(Overlap), s);
+  compact_overlaps(e, d_ovl, d_keep, ks.slot, O, out.ovl.as<Overlap>() + acc_n);
   out.n_overlaps = acc_n + m;
   return m;
 }
@@ -407,7 +392,7 @@ void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out) {
     RVN_HIP(hipMemsetAsync(d_keep, 1, acc_n, s));
     dedup_kernel<<<div_up(acc_n, 256), 256, 0, s>>>(out.ovl.as<Overlap>(), acc_n, d_keep);
     RVN_LAUNCH_CHECK();
-    acc_n = compact(e, out.ovl, acc_n, d_keep, e.p2_slot, e.p2_tmp_ovl);
+    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_keep, e.p2_slot, e.p2_tmp_ovl);
   }
   if (out.n) {
     merge_invalid_kernel<<<div_up(out.n, 256), 256, 0, s>>>(d_regions, out.contained.as<u8>(), out.n);
@@ -417,7 +402,7 @@ void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out) {
     u8* d_ok = e.p2_ok.get<u8>(acc_n + 16);
     update_kernel<<<div_up(acc_n, 256), 256, 0, s>>>(out.ovl.as<Overlap>(), acc_n, d_regions, d_ok);
     RVN_LAUNCH_CHECK();
-    acc_n = compact(e, out.ovl, acc_n, d_ok, e.p2_slot, e.p2_tmp_ovl);
+    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_ok, e.p2_slot, e.p2_tmp_ovl);
   }
   RVN_HIP(rvn_stream_sync(s));
   out.n_overlaps = acc_n;
@@ -438,17 +423,11 @@ void second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_
 void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u64 O, const u32* h_begin, const u32* h_end,
                            const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd) {
   hipStream_t s = e.stream;
-  const u32 n = R.n;
   if (O == 0) return;
-  PileRegion* d_regions = upload_regions(e, h_begin, h_end, h_invalid, n);
-  std::vector<u32> index_of(n);
-  for (u32 i = 0; i < n; ++i) index_of[i] = i;
-  u32* d_index_of = e.p2_index_of.get<u32>(static_cast<size_t>(n) + 1);
-  RVN_HIP(hipMemcpyAsync(d_index_of, index_of.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
-  Overlap* d_ovl = e.p2_tmp_ovl.get<Overlap>(O + 1);
+  PileRegion* d_regions = upload_pile_regions(e, e.p2_regions, h_begin, h_end, h_invalid, R.n);
+  Overlap* d_ovl = upload(e.p2_tmp_ovl, h_ovl, O, s);
   u8* d_ok = e.p2_ok.get<u8>(O + 16);
-  RVN_HIP(hipMemcpyAsync(d_ovl, h_ovl, O * sizeof(Overlap), hipMemcpyHostToDevice, s));
-  update_and_identity(e, R, d_ovl, O, d_regions, d_index_of, identity, d_ok);
+  update_and_identity(e, R, d_ovl, O, d_regions, nullptr, identity, d_ok);  // ids are indices
   RVN_HIP(hipMemcpyAsync(h_ok, d_ok, O, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(h_upd, d_ovl, O * sizeof(Overlap), hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));

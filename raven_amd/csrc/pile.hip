@@ -316,8 +316,7 @@ void piles_merge(Engine& e, const ReadsDev& r, const MapOut& mo, u32 kmax, PileS
     RVN_KLAUNCH(kKKeptWrite, kept_write_kernel<<<div_up(n, 4), 256, 0, s>>>(list, list_off, skeys, ps.kept.as<Overlap>(),
                                                    ps.kept_off.as<u32>(), new_kept_off, n, kept_new));
     // adopt: kept <- kept_new, kept_off <- new_kept_off
-    std::swap(ps.kept.ptr, ps.tmp5.ptr);
-    std::swap(ps.kept.cap, ps.tmp5.cap);
+    ps.kept.swap(ps.tmp5);
     u32* ko = ps.kept_off.get<u32>(static_cast<size_t>(n) + 1);
     RVN_HIP(hipMemcpyAsync(ko, new_kept_off, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToDevice, s));
     ps.kept_total = K;

@@ -313,10 +313,9 @@ void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_las
     std::swap(a.first, b.first);
     std::swap(a.last, b.last);
     std::swap(a.count, b.count);
-    for (auto pr : {std::make_pair(&a.val, &b.val), std::make_pair(&a.org, &b.org), std::make_pair(&a.read_off, &b.read_off)}) {
-      std::swap(pr.first->ptr, pr.second->ptr);
-      std::swap(pr.first->cap, pr.second->cap);
-    }
+    a.val.swap(b.val);
+    a.org.swap(b.org);
+    a.read_off.swap(b.read_off);
   };
   Overlap* d_best = e.pl_best.get<Overlap>(static_cast<size_t>(R.n) + 1);
   u32* d_best_t = e.pl_best_t.get<u32>(static_cast<size_t>(R.n) + 1);

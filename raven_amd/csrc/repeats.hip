@@ -312,18 +312,6 @@ __global__ void repeat_check_kernel(const Overlap* __restrict__ ovl, u64 m, cons
   }
   keep[i] = hit ? 0 : 1;
 }
-__global__ void repeat_compact_kernel(const Overlap* __restrict__ in, const u8* __restrict__ keep, const u32* __restrict__ slot,
-                                      u64 m, Overlap* __restrict__ out) {
-  const u64 i = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < m && keep[i]) out[slot[i]] = in[i];
-}
-
-template <typename T>
-T* upload(DevBuf& b, const T* h, size_t count, hipStream_t s) {
-  T* d = b.get<T>(count + 1);
-  if (count) RVN_HIP(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-  return d;
-}
 
 int key_bits_for(u32 n) {
   int b = 0;
@@ -348,16 +336,13 @@ void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32
         regions, keep, slot, sort_tmp, scan_tmp;
   } B;
   const u64 cells = h_cov_off[n], kcells = h_kmer_off[n];
-  std::vector<PileRegion> h_reg(n);
   std::vector<u32> h_bc(n), h_ec(n);
   for (u32 i = 0; i < n; ++i) {
-    h_reg[i] = PileRegion{h_begin[i], h_end[i], h_invalid[i] ? 1u : 0u};
     h_bc[i] = h_begin[i] >> 4;  // Pile::begin_ / end_
     h_ec[i] = h_end[i] >> 4;
   }
   Overlap* d_ovl = upload(B.ovl, h_ovl, m, s);
-  B.ovl2.get<Overlap>(m + 1);
-  const PileRegion* d_reg = upload(B.reg, h_reg.data(), n, s);
+  const PileRegion* d_reg = upload_pile_regions(e, B.reg, h_begin, h_end, h_invalid, n);
   const u32* d_begin = upload(B.begin, h_bc.data(), n, s);
   const u32* d_end = upload(B.end, h_ec.data(), n, s);
   RepeatJob J{};
@@ -464,19 +449,15 @@ void resolve_repeat_induced_overlaps(Engine& e, const Overlap* h_ovl, u64 m, u32
     u8* d_keep = B.keep.get<u8>(m + 1);
     repeat_check_kernel<<<div_up(m, 256), 256, 0, s>>>(d_ovl, m, d_roff, d_regions, d_begin, d_end, d_keep);
     RVN_LAUNCH_CHECK();
-    u32* d_slot = B.slot.get<u32>(m + 2);
-    exclusive_scan_u8_u32(d_keep, d_slot, m, B.scan_tmp, s);
-    const u64 kept = read_back(e, d_slot + m, 4);
+    const KeptSlots ks = kept_slots(e, d_keep, m, B.slot);
+    const u64 kept = ks.kept;
     if (kept == m) {  // nothing removed: the regions of this iteration are the piles' final state
       res.reg.assign(2ULL * total, 0);
       if (total) RVN_HIP(hipMemcpyAsync(res.reg.data(), d_regions, 8ULL * total, hipMemcpyDeviceToHost, s));
       break;
     }
-    Overlap* d_out = B.ovl2.as<Overlap>();
-    repeat_compact_kernel<<<div_up(m, 256), 256, 0, s>>>(d_ovl, d_keep, d_slot, m, d_out);
-    RVN_LAUNCH_CHECK();
-    std::swap(B.ovl.ptr, B.ovl2.ptr);
-    std::swap(B.ovl.cap, B.ovl2.cap);
+    compact_overlaps(e, d_ovl, d_keep, ks.slot, m, B.ovl2.get<Overlap>(kept + 1));
+    B.ovl.swap(B.ovl2);
     d_ovl = B.ovl.as<Overlap>();
     res.removed += m - kept;
     m = kept;
@@ -508,14 +489,9 @@ int rvn_resolve_repeat_induced_overlaps(rvn_engine* h, const rvn_overlap* overla
         (coverage_offsets[n_piles] && !coverage) || (kmers_offsets[n_piles] && !kmers))
       return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: NULL argument");
     *out = nullptr;
-    if (coverage_offsets[0] != 0 || kmers_offsets[0] != 0)
-      return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must start at 0");
-    for (u32 i = 0; i < n_piles; ++i) {
-      if (coverage_offsets[i + 1] < coverage_offsets[i] || kmers_offsets[i + 1] < kmers_offsets[i])
-        return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: offsets must not decrease");
-      if (coverage_offsets[i + 1] - coverage_offsets[i] >= (1u << 27) || kmers_offsets[i + 1] - kmers_offsets[i] >= (1u << 27))
-        return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: a pile of 2^27 cells or more");
-    }
+    const char* csr = csr_offsets_error(coverage_offsets, n_piles, kMaxPileCells);
+    if (!csr) csr = csr_offsets_error(kmers_offsets, n_piles, kMaxPileCells);
+    if (csr) return fail(RVN_EINVAL, std::string("[raven_hip] rvn_resolve_repeat_induced_overlaps: ") + csr);
     for (u64 x = 0; x < n_overlaps; ++x)
       if (overlaps[x].lhs_id >= n_piles || overlaps[x].rhs_id >= n_piles)
         return fail(RVN_EINVAL, "[raven_hip] rvn_resolve_repeat_induced_overlaps: overlap of an unknown pile");

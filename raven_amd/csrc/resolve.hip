@@ -260,19 +260,11 @@ void compact_lists(Engine& e, ResolveState& st, Scratch& S, u8* d_keep) {
   if (m == 0) return;
   keep_valid_kernel<<<div_up(m, 256), 256, 0, s>>>(st.ovl.as<Overlap>(), m, st.invalid.as<u8>(), d_keep);
   RVN_LAUNCH_CHECK();
-  u32* d_slot = S.slot.get<u32>(m + 2);
-  exclusive_scan_u8_u32(d_keep, d_slot, m, e.scan_tmp, s);
-  const u64 kept = read_back(e, d_slot + m, 4);
-  Overlap* d_out = S.ovl2.get<Overlap>(kept + 1);
-  compact_overlaps(e, st.ovl.as<Overlap>(), d_keep, d_slot, m, d_out);
+  st.n_overlaps = compact_overlap_list(e, st.ovl, m, d_keep, S.slot, S.ovl2);
   u32* d_off2 = S.off2.get<u32>(static_cast<size_t>(n) + 2);
-  new_offsets_kernel<<<div_up(static_cast<u64>(n) + 1, 256), 256, 0, s>>>(st.off.as<u32>(), d_slot, n, d_off2);
+  new_offsets_kernel<<<div_up(static_cast<u64>(n) + 1, 256), 256, 0, s>>>(st.off.as<u32>(), S.slot.as<u32>(), n, d_off2);
   RVN_LAUNCH_CHECK();
-  std::swap(st.ovl.ptr, S.ovl2.ptr);
-  std::swap(st.ovl.cap, S.ovl2.cap);
-  std::swap(st.off.ptr, S.off2.ptr);
-  std::swap(st.off.cap, S.off2.cap);
-  st.n_overlaps = kept;
+  st.off.swap(S.off2);
 }
 
 void apply_marks(Engine& e, ResolveState& st, const u8* d_mark, u64* d_cnt) {
@@ -287,13 +279,8 @@ void phase_contained(Engine& e, ResolveState& st, Scratch& S, const ReadsDev* R,
   const u32 n = st.n;
   u8* d_keep = S.keep.get<u8>(st.n_overlaps + 16);
   if (identity != 0 && st.n_overlaps) {  // :162-217
-    std::vector<u32> index_of(n);
-    for (u32 i = 0; i < n; ++i) index_of[i] = i;
-    u32* d_index_of = e.p2_index_of.get<u32>(static_cast<size_t>(n) + 1);
-    RVN_HIP(hipMemcpyAsync(d_index_of, index_of.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
-    RVN_HIP(rvn_stream_sync(s));
     const u64 before = st.n_overlaps;
-    update_and_identity(e, *R, st.ovl.as<Overlap>(), st.n_overlaps, st.pr.as<PileRegion>(), d_index_of, identity, d_keep);
+    update_and_identity(e, *R, st.ovl.as<Overlap>(), st.n_overlaps, st.pr.as<PileRegion>(), nullptr, identity, d_keep);  // ids are indices
     compact_lists(e, st, S, d_keep);
     st.stats.dropped_by_filter += before - st.n_overlaps;
   }
@@ -399,11 +386,6 @@ void copy_dd(DevBuf& dst, const DevBuf& src, size_t count, hipStream_t s) {
   T* d = dst.get<T>(count + 16);
   if (count) RVN_HIP(hipMemcpyAsync(d, src.ptr, count * sizeof(T), hipMemcpyDeviceToDevice, s));
 }
-template <typename T>
-void copy_hd(DevBuf& dst, const T* src, size_t count, hipStream_t s) {
-  T* d = dst.get<T>(count + 16);
-  if (count) RVN_HIP(hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-}
 
 }  // namespace
 
@@ -438,18 +420,18 @@ std::shared_ptr<ResolveState> resolve_state_of_arrays(Engine& e, const Overlap* 
   hipStream_t s = e.stream;
   auto st = std::make_shared<ResolveState>();
   st->n = n;
-  copy_hd(st->begin, begin, n, s);
-  copy_hd(st->end, end, n, s);
-  copy_hd(st->median, median, n, s);
-  copy_hd(st->invalid, invalid, n, s);
-  copy_hd(st->roff, roff, static_cast<size_t>(n) + 1, s);
+  upload(st->begin, begin, n, s);
+  upload(st->end, end, n, s);
+  upload(st->median, median, n, s);
+  upload(st->invalid, invalid, n, s);
+  upload(st->roff, roff, static_cast<size_t>(n) + 1, s);
   st->regions_total = roff[n];
-  copy_hd(st->regions, regions, 2ULL * roff[n], s);
+  upload(st->regions, regions, 2ULL * roff[n], s);
   st->n_overlaps = off[n];
-  copy_hd(st->ovl, ovl, off[n], s);
-  copy_hd(st->off, off, static_cast<size_t>(n) + 1, s);
-  copy_hd(st->own_cov, cov, cov_off[n], s);
-  copy_hd(st->own_cov_off, cov_off, static_cast<size_t>(n) + 1, s);
+  upload(st->ovl, ovl, off[n], s);
+  upload(st->off, off, static_cast<size_t>(n) + 1, s);
+  upload(st->own_cov, cov, cov_off[n], s);
+  upload(st->own_cov_off, cov_off, static_cast<size_t>(n) + 1, s);
   st->cov = st->own_cov.as<u16>();
   st->cov_off = st->own_cov_off.as<u64>();
   st->cov_words = cov_off[n];
@@ -573,12 +555,12 @@ int rvn_resolve_contained_and_chimeric(rvn_engine* h, const rvn_reads* rr, const
       if (!rr) return bad("the identity filter needs the reads");
       if (rr->r.n != n_piles || !rr->r.ids_are_indices) return bad("the reads are not the ones of these piles (ids[i] == i)");
     }
-    if (offsets[0] != 0 || coverage_offsets[0] != 0 || region_offsets[0] != 0) return bad("offsets must start at 0");
+    const char* csr = csr_offsets_error(offsets, n_piles, kNoCsrLimit);
+    if (!csr) csr = csr_offsets_error(coverage_offsets, n_piles, kMaxPileCells);
+    if (!csr) csr = csr_offsets_error(region_offsets, n_piles, kNoCsrLimit);
+    if (csr) return bad(csr);
     for (u32 i = 0; i < n_piles; ++i) {
-      if (offsets[i + 1] < offsets[i] || coverage_offsets[i + 1] < coverage_offsets[i] || region_offsets[i + 1] < region_offsets[i])
-        return bad("offsets must not decrease");
       const u64 len = coverage_offsets[i + 1] - coverage_offsets[i];
-      if (len >= (1u << 27)) return bad("a pile of 2^27 cells or more");
       if (begin[i] > end[i] || end[i] > len) return bad("a valid region outside its pile");
       for (u32 k = region_offsets[i]; k < region_offsets[i + 1]; ++k)
         if (regions[2 * k] > regions[2 * k + 1] || regions[2 * k + 1] >= len) return bad("a chimeric region outside its pile");

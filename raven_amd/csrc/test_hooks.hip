@@ -444,6 +444,27 @@ int rvn_test_radix_sort_pairs(int variant, uint64_t* keys, uint64_t* values, uin
   });
 }
 
+int rvn_test_compact_overlap_list(const rvn_overlap* in, uint64_t n, const uint8_t* keep1, const uint8_t* keep2,
+                                  rvn_overlap* out, uint64_t* n_out, uint32_t* slot) {
+  if ((n && (!in || !keep1 || !out)) || !n_out || !slot || n >= (1ULL << 32))
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_compact_overlap_list: bad argument");
+  return with_own_engine([&](Engine& e) -> int {
+    DevBuf list, spare, slots, keep;
+    upload(list, reinterpret_cast<const Overlap*>(in), n, e.stream);
+    u64 m = n, kept = compact_overlap_list(e, list, m, upload(keep, keep1, m, e.stream), slots, spare);
+    if (keep2) {
+      m = kept;
+      kept = compact_overlap_list(e, list, m, upload(keep, keep2, m, e.stream), slots, spare);
+    }
+    RVN_HIP(rvn_stream_sync(e.stream));
+    slot[0] = 0;
+    if (m) RVN_HIP(hipMemcpy(slot, slots.ptr, (m + 1) * 4, hipMemcpyDeviceToHost));
+    if (kept) RVN_HIP(hipMemcpy(out, list.ptr, kept * sizeof(Overlap), hipMemcpyDeviceToHost));
+    *n_out = kept;
+    return RVN_OK;
+  });
+}
+
 int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_t in_offset_items, uint32_t out_offset_items,
                             uint64_t* out) {
   if (variant < 0 || variant > 2 || (n && !in) || !out || n >= (1ULL << 32) || in_offset_items > 64 || out_offset_items > 64)

@@ -192,6 +192,7 @@ _TEST_SIGNATURES = {
     "rvn_test_match_probe": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _i32, _i32, _pp, _pp, _vp, _vp, _pu64]),
     "rvn_test_radix_sort_pairs": (_i32, [_i32, _vp, _vp, _u64, _i32, _i32]),
     "rvn_test_exclusive_scan": (_i32, [_i32, _vp, _u64, _u32, _u32, _vp]),
+    "rvn_test_compact_overlap_list": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1277,6 +1278,26 @@ def test_exclusive_scan(variant, values, in_offset=0, out_offset=0):
     _test_check(test_lib().rvn_test_exclusive_scan(SCAN_VARIANTS[variant], _p(a), a.shape[0], int(in_offset), int(out_offset),
                                                    _p(out)))
     return out
+
+
+def test_compact_overlap_list(overlaps, keep1, keep2=None):
+    """compact_overlap_list (pass2.hip) on host overlaps (rvn_test_compact_overlap_list): keep1[n], then keep2 on the
+    survivors when given.  Returns (survivors, the scan of the last application: uint32[its flags + 1])."""
+    o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)
+    k1 = np.ascontiguousarray(keep1, dtype=np.uint8)
+    assert k1.shape == o.shape and o.ndim == 1
+    m = o.shape[0]
+    k2 = None
+    if keep2 is not None:
+        k2 = np.ascontiguousarray(keep2, dtype=np.uint8)
+        m = int(k1.sum())
+        assert k2.shape == (m,)
+    out = np.zeros(o.shape[0], dtype=OVERLAP_DTYPE)
+    slot = np.zeros(o.shape[0] + 1, dtype=np.uint32)
+    n_out = C.c_uint64(0)
+    _test_check(test_lib().rvn_test_compact_overlap_list(_p(o), o.shape[0], _p(k1), _p(k2), _p(out),
+                                                         C.byref(n_out), _p(slot)))
+    return out[:n_out.value], slot[:m + 1]
 
 
 class HookEngine:
