@@ -135,6 +135,10 @@ int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_
  * nothing: slot[0] = 0).  Engine of its own (device 0), no kernel launched from here. */
 int rvn_test_compact_overlap_list(const rvn_overlap* in, uint64_t n, const uint8_t* keep1, const uint8_t* keep2,
                                   rvn_overlap* out, uint64_t* n_out, uint32_t* slot);
+/* The scratch an engine holds: the sum of the capacities of every device buffer that rvn_engine_release_scratch hands back
+ * (every buffer the engine's state groups name for release; the read sets and pass handles are not the engine's).  0 right
+ * after a release.  It only reads the handle, so h may also be an engine made by libraven_hip.so of the same build. */
+int rvn_test_engine_scratch_bytes(rvn_engine* h, uint64_t* bytes);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

@@ -30,21 +30,21 @@ int rvn_engine_filter(rvn_engine* h, double f) {
   });
 }
 
-uint32_t rvn_engine_occurrence(const rvn_engine* h) { return h ? h->e.index.occurrence : 0; }
+uint32_t rvn_engine_occurrence(const rvn_engine* h) { return h ? h->e.sketch.index.occurrence : 0; }
 
 int rvn_engine_set_occurrence(rvn_engine* h, uint32_t occurrence) {
   if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
-  h->e.index.occurrence = occurrence;
+  h->e.sketch.index.occurrence = occurrence;
   return RVN_OK;
 }
 
 int rvn_engine_map_batch(rvn_engine* h, const rvn_reads* r, uint32_t first, uint32_t last, int avoid_equal,
                          int avoid_symmetric, int minhash, int want_filtered, uint64_t* n_overlaps) {
   return guarded(h, h && r && first <= last && last <= r->r.n, "[raven_hip] rvn_engine_map_batch: bad range", [&](Engine& e) -> int {
-    map_batch(e, r->r, first, last, avoid_equal != 0, avoid_symmetric != 0, minhash != 0, want_filtered != 0, e.map_out);
-    e.c_intervals += e.map_out.n_intervals;
+    map_batch(e, r->r, first, last, avoid_equal != 0, avoid_symmetric != 0, minhash != 0, want_filtered != 0, e.map.out);
+    e.c_intervals += e.map.out.n_intervals;
     RVN_HIP(rvn_stream_sync(e.stream));
-    if (n_overlaps) *n_overlaps = e.map_out.n_overlaps;
+    if (n_overlaps) *n_overlaps = e.map.out.n_overlaps;
     return RVN_OK;
   });
 }
@@ -55,7 +55,7 @@ int map_fetch(rvn_engine* h, rvn_overlap* overlaps, uint32_t* read_offsets, hipM
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    MapOut& m = e.map_out;
+    MapOut& m = e.map.out;
     RVN_HIP(hipSetDevice(e.device));
     if (overlaps && m.n_overlaps) put(e, overlaps, m.ovl.ptr, m.n_overlaps * sizeof(Overlap), kind);
     if (read_offsets) put(e, read_offsets, m.ovl_read_off.ptr, (static_cast<size_t>(m.last - m.first) + 1) * 4, kind);
@@ -76,7 +76,7 @@ int rvn_engine_map_fetch_filtered(rvn_engine* h, uint32_t* positions, uint32_t* 
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    MapOut& m = e.map_out;
+    MapOut& m = e.map.out;
     RVN_HIP(hipSetDevice(e.device));
     const u64 nq = m.n_query;
     const u32 nr = m.last - m.first;
@@ -85,9 +85,9 @@ int rvn_engine_map_fetch_filtered(rvn_engine* h, uint32_t* positions, uint32_t* 
     std::vector<u32> roff(static_cast<size_t>(nr) + 1, 0);
     if (nq) {
       RVN_HIP(hipMemcpy(flags.data(), m.filtered.ptr, nq, hipMemcpyDeviceToHost));
-      RVN_HIP(hipMemcpy(org.data(), e.query_sketch.org.ptr, nq * 8, hipMemcpyDeviceToHost));
+      RVN_HIP(hipMemcpy(org.data(), e.sketch.query_sketch.org.ptr, nq * 8, hipMemcpyDeviceToHost));
     }
-    RVN_HIP(hipMemcpy(roff.data(), e.query_sketch.read_off.ptr, roff.size() * 4, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(roff.data(), e.sketch.query_sketch.read_off.ptr, roff.size() * 4, hipMemcpyDeviceToHost));
     u64 tot = 0;
     for (u32 i = 0; i < nr; ++i) {
       if (read_offsets) read_offsets[i] = static_cast<u32>(tot);
@@ -218,10 +218,10 @@ int rvn_find_overlaps_and_create_piles(rvn_engine* h, const rvn_reads* rr, doubl
         bytes += r.h_len[k];
         if (k != i && bytes < flush_bases) continue;
         bytes = 0;
-        map_batch(e, r, flush_first, k + 1, true, true, true, false, e.map_out);
+        map_batch(e, r, flush_first, k + 1, true, true, true, false, e.map.out);
         lap("map_batch");
-        e.c_intervals += e.map_out.n_intervals;
-        piles_merge(e, r, e.map_out, kmax, p->ps);
+        e.c_intervals += e.map.out.n_intervals;
+        piles_merge(e, r, e.map.out, kmax, p->ps);
         lap("piles_merge");
         flush_first = k + 1;
       }
@@ -438,9 +438,9 @@ int rvn_edit_distance_batch(rvn_engine* h, const rvn_reads* r, const rvn_ed_pair
 
 int rvn_engine_sketch(rvn_engine* h, const rvn_reads* r, uint32_t first, uint32_t last, int minhash, uint64_t* count) {
   return guarded(h, h && r && first <= last && last <= r->r.n, "[raven_hip] rvn_engine_sketch: bad range", [&](Engine& e) -> int {
-    sketch_range(e, r->r, first, last, minhash != 0, e.query_sketch);
+    sketch_range(e, r->r, first, last, minhash != 0, e.sketch.query_sketch);
     RVN_HIP(rvn_stream_sync(e.stream));
-    if (count) *count = e.query_sketch.count;
+    if (count) *count = e.sketch.query_sketch.count;
     return RVN_OK;
   });
 }
@@ -449,7 +449,7 @@ int rvn_engine_sketch_fetch(rvn_engine* h, uint64_t* values, uint64_t* origins, 
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    Sketch& s = e.query_sketch;
+    Sketch& s = e.sketch.query_sketch;
     RVN_HIP(hipSetDevice(e.device));
     fetch_values(e, s.val, s.count, values);
     if (origins && s.count) RVN_HIP(hipMemcpy(origins, s.org.ptr, s.count * 8, hipMemcpyDeviceToHost));
@@ -462,8 +462,8 @@ int rvn_engine_sketch_fetch(rvn_engine* h, uint64_t* values, uint64_t* origins, 
 
 int rvn_engine_index_size(const rvn_engine* h, uint64_t* n_minimizers, uint64_t* n_keys) {
   if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
-  if (n_minimizers) *n_minimizers = h->e.index.m;
-  if (n_keys) *n_keys = h->e.index.u;
+  if (n_minimizers) *n_minimizers = h->e.sketch.index.m;
+  if (n_keys) *n_keys = h->e.sketch.index.u;
   return RVN_OK;
 }
 
@@ -471,7 +471,7 @@ int rvn_engine_index_fetch(rvn_engine* h, uint64_t* values, uint64_t* origins) {
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    Index& ix = e.index;
+    Index& ix = e.sketch.index;
     RVN_HIP(hipSetDevice(e.device));
     fetch_values(e, ix.s_val[ix.cur], ix.m, values);
     if (origins && ix.m) {

@@ -116,10 +116,10 @@ int rvn_polish_set_best(rvn_engine* h, const rvn_overlap* best, const uint32_t* 
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h || (n_reads && (!best || !best_target))) return fail(RVN_EINVAL, "[raven_hip] rvn_polish_set_best: NULL argument");
     Engine& e = h->e;
-    e.polish_given_best.resize(n_reads);
-    e.polish_given_best_t.assign(best_target, best_target + n_reads);
-    if (n_reads) std::memcpy(e.polish_given_best.data(), best, static_cast<size_t>(n_reads) * sizeof(Overlap));
-    e.polish_given_valid = true;
+    e.polish.given_best.resize(n_reads);
+    e.polish.given_best_t.assign(best_target, best_target + n_reads);
+    if (n_reads) std::memcpy(e.polish.given_best.data(), best, static_cast<size_t>(n_reads) * sizeof(Overlap));
+    e.polish.given_valid = true;
     return RVN_OK;
   });
 }
@@ -222,41 +222,41 @@ uint64_t rvn_polish_set_chunk_windows(rvn_engine* h, uint64_t windows) {
 }
 
 int rvn_polish_target_reads(const rvn_engine* h, uint32_t* counts, uint32_t n_targets) {
-  if (!h || !counts || n_targets != h->e.polish_target_reads.size())
+  if (!h || !counts || n_targets != h->e.polish.target_reads.size())
     return fail(RVN_EINVAL, "[raven_hip] rvn_polish_target_reads: no polishing round with that many targets");
-  for (uint32_t i = 0; i < n_targets; ++i) counts[i] = h->e.polish_target_reads[i];
+  for (uint32_t i = 0; i < n_targets; ++i) counts[i] = h->e.polish.target_reads[i];
   return RVN_OK;
 }
 
 void rvn_poa_phase_cycles(const rvn_engine* h, uint64_t out[6]) {
-  for (int i = 0; i < 6; ++i) out[i] = h ? h->e.poa_phase_cycles[i] : 0;
+  for (int i = 0; i < 6; ++i) out[i] = h ? h->e.poa.phase_cycles[i] : 0;
 }
 
 int rvn_poa_set_mode(rvn_engine* h, int mode) {
   if (!h) return -1;
-  const int prev = h->e.poa_mode;
-  if ((mode >= 0 && mode <= 4) || mode == 9) h->e.poa_mode = mode;
+  const int prev = h->e.poa.mode;
+  if ((mode >= 0 && mode <= 4) || mode == 9) h->e.poa.mode = mode;
   return prev;
 }
 
-uint32_t rvn_poa_fallback_windows(const rvn_engine* h) { return h ? h->e.poa_fallback_windows : 0; }
-uint32_t rvn_poa_wide_windows(const rvn_engine* h) { return h ? h->e.poa_wide_windows : 0; }
-uint32_t rvn_poa_narrow_windows(const rvn_engine* h) { return h ? h->e.poa_narrow_windows : 0; }
+uint32_t rvn_poa_fallback_windows(const rvn_engine* h) { return h ? h->e.poa.fallback_windows : 0; }
+uint32_t rvn_poa_wide_windows(const rvn_engine* h) { return h ? h->e.poa.wide_windows : 0; }
+uint32_t rvn_poa_narrow_windows(const rvn_engine* h) { return h ? h->e.poa.narrow_windows : 0; }
 
 int rvn_polish_fetch_layers(rvn_engine* h, uint32_t* out, uint64_t cap, uint64_t* n_out) {
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h || !n_out) return fail(RVN_EINVAL, "[raven_hip] rvn_polish_fetch_layers: NULL argument");
     Engine& e = h->e;
     RVN_HIP(hipSetDevice(e.device));
-    const u32 nw = e.polish_last_windows;
-    const u64 nl = e.polish_last_layers;
+    const u32 nw = e.polish.last_layers.windows;
+    const u64 nl = e.polish.last_layers.layers;
     std::vector<PoaWindow> wins(nw);
     std::vector<PoaLayer> lays(nl);
     std::vector<u8> ok(nl, 1);
-    if (nw) RVN_HIP(hipMemcpy(wins.data(), e.pl_wins.ptr, nw * sizeof(PoaWindow), hipMemcpyDeviceToHost));
-    if (nl) RVN_HIP(hipMemcpy(lays.data(), e.pl_lays.ptr, nl * sizeof(PoaLayer), hipMemcpyDeviceToHost));
-    if (nl && e.polish_last_has_ok) RVN_HIP(hipMemcpy(ok.data(), e.pl_ok.ptr, nl, hipMemcpyDeviceToHost));
-    const std::vector<u64>& ro = e.polish_last_read_off;
+    if (nw) RVN_HIP(hipMemcpy(wins.data(), e.polish.wins.ptr, nw * sizeof(PoaWindow), hipMemcpyDeviceToHost));
+    if (nl) RVN_HIP(hipMemcpy(lays.data(), e.polish.lays.ptr, nl * sizeof(PoaLayer), hipMemcpyDeviceToHost));
+    if (nl && e.polish.last_layers.has_ok) RVN_HIP(hipMemcpy(ok.data(), e.polish.ok.ptr, nl, hipMemcpyDeviceToHost));
+    const std::vector<u64>& ro = e.polish.last_layers.read_off;
     u64 n = 0;
     for (u32 i = 0; i < nw; ++i) {
       for (u32 x = 1; x < wins[i].n_layers; ++x) {  // layer 0 = backbone
@@ -266,7 +266,7 @@ int rvn_polish_fetch_layers(rvn_engine* h, uint32_t* out, uint64_t cap, uint64_t
         if (out && n < cap) {
           const u64 read = static_cast<u64>(std::upper_bound(ro.begin(), ro.end(), L.code_off) - ro.begin()) - 1;
           uint32_t* o = out + 7 * n;
-          o[0] = static_cast<uint32_t>(e.polish_last_w0 + i);
+          o[0] = static_cast<uint32_t>(e.polish.last_layers.w0 + i);
           o[1] = static_cast<uint32_t>(read);
           o[2] = L.q_begin;
           o[3] = L.len;

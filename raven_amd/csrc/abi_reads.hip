@@ -68,8 +68,8 @@ int reads_from_device_codes(Engine& e, const u8* d_codes, const std::vector<u64>
     woff[i + 1] = woff[i] + (static_cast<u64>(lens[i]) + 31) / 32;
   }
   const u64 n_words = woff[n], n_codes = n ? boff[n] - boff[0] : 0;
-  u64* d_boff = e.tmp_b.get<u64>(static_cast<size_t>(n) + 1);
-  u64* d_woff = e.tmp_c.get<u64>(static_cast<size_t>(n) + 1);
+  u64* d_boff = e.scratch.tmp_b.get<u64>(static_cast<size_t>(n) + 1);
+  u64* d_woff = e.scratch.tmp_c.get<u64>(static_cast<size_t>(n) + 1);
   RVN_HIP(hipMemcpy(d_boff, boff.data(), boff.size() * 8, hipMemcpyHostToDevice));
   RVN_HIP(hipMemcpy(d_woff, woff.data(), woff.size() * 8, hipMemcpyHostToDevice));
   std::unique_ptr<rvn_reads> rr(new rvn_reads());
@@ -115,7 +115,7 @@ int rvn_reads_upload_codes(rvn_engine* h, const uint8_t* codes, const uint64_t* 
         return fail(RVN_EINVAL, "[raven_hip] rvn_reads_upload_codes: bad offsets");
     const u64 n_codes = n ? offsets[n] - offsets[0] : 0;
     // bases to HBM as bytes, packed there (one thread per word)
-    u8* d_codes = e.tmp_a.get<u8>(n_codes + 16);
+    u8* d_codes = e.scratch.tmp_a.get<u8>(n_codes + 16);
     if (n_codes) RVN_HIP(hipMemcpy(d_codes, codes + (n ? offsets[0] : 0), n_codes, hipMemcpyHostToDevice));
     std::vector<u64> boff(static_cast<size_t>(n) + 1, 0);
     for (u32 i = 0; i <= n && n; ++i) boff[i] = offsets[i] - offsets[0];
@@ -132,10 +132,10 @@ int rvn_polish_output_as_reads(rvn_engine* h, rvn_reads** out) {
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h || !out) return fail(RVN_EINVAL, "[raven_hip] rvn_polish_output_as_reads: NULL argument");
     Engine& e = h->e;
-    if (!e.pl_last_valid) return fail(RVN_EINVAL, "[raven_hip] rvn_polish_output_as_reads: no complete polishing round's consensus is resident");
+    if (!e.polish.last_cons.valid) return fail(RVN_EINVAL, "[raven_hip] rvn_polish_output_as_reads: no complete polishing round's consensus is resident");
     RVN_HIP(hipSetDevice(e.device));
-    const u32 n = static_cast<u32>(e.pl_last_off.size() - 1);
-    return reads_from_device_codes(e, e.pl_final.ptr ? reinterpret_cast<const u8*>(e.pl_final.ptr) : nullptr, e.pl_last_off, nullptr, n, out);
+    const u32 n = static_cast<u32>(e.polish.last_cons.off.size() - 1);
+    return reads_from_device_codes(e, e.polish.stitched.ptr ? reinterpret_cast<const u8*>(e.polish.stitched.ptr) : nullptr, e.polish.last_cons.off, nullptr, n, out);
   });
 }
 

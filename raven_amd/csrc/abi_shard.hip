@@ -14,16 +14,16 @@ int rvn_shard_sketch(rvn_engine* h, const rvn_reads* rr, int index_minhash, uint
   return guarded(h, h && rr && count, "[raven_hip] rvn_shard_sketch: NULL argument", [&](Engine& e) -> int {
     const ReadsDev& r = rr->r;
     StageTimer t(e, StageTimes::kSketch);
-    e.query_ready = false;
-    sketch_raw(e, r, 0, r.n, e.raw_sketch);
+    e.sketch.query_ready = {};
+    sketch_raw(e, r, 0, r.n, e.sketch.raw_sketch);
     if (index_minhash) {
-      sketch_minhash(e, r, e.raw_sketch, e.index_sketch);
-      e.shard_sketch_minhash = true;
-      *count = e.index_sketch.count;
+      sketch_minhash(e, r, e.sketch.raw_sketch, e.sketch.index_sketch);
+      e.sketch.shard_sketch_minhash = true;
+      *count = e.sketch.index_sketch.count;
     } else {
-      e.join_query_count = sketch_flag_queries(e, r, e.raw_sketch);  // minhash-selected entries get kQueryFlag
-      e.shard_sketch_minhash = false;
-      *count = e.raw_sketch.count;
+      e.sketch.join_query_count = sketch_flag_queries(e, r, e.sketch.raw_sketch);  // minhash-selected entries get kQueryFlag
+      e.sketch.shard_sketch_minhash = false;
+      *count = e.sketch.raw_sketch.count;
     }
     for (u32 i = 0; i < r.n; ++i) e.c_index_bases += r.h_len[i];
     t.stop();
@@ -49,10 +49,10 @@ int rvn_shard_sketch_range(rvn_engine* h, const rvn_reads* rr, uint32_t first, u
     RVN_HIP(hipSetDevice(e.device));
     UseTimers ut(e);
     StageTimer t(e, StageTimes::kSketch);
-    e.query_ready = false;
+    e.sketch.query_ready = {};
     *count = 0;
-    e.shard_sketch_minhash = (index_minhash != 0) || (foreign != 0);
-    Sketch& res = e.shard_sketch_minhash ? e.index_sketch : e.raw_sketch;
+    e.sketch.shard_sketch_minhash = (index_minhash != 0) || (foreign != 0);
+    Sketch& res = e.sketch.shard_sketch_minhash ? e.sketch.index_sketch : e.sketch.raw_sketch;
     res.count = 0;
     if (first == last) {
       t.stop();
@@ -80,42 +80,42 @@ int rvn_shard_sketch_range(rvn_engine* h, const rvn_reads* rr, uint32_t first, u
       }
       cuts.push_back(last);
       if (cuts.size() == 2) {
-        sketch_raw(e, r, first, last, e.raw_sketch);
-        sketch_minhash(e, r, e.raw_sketch, e.index_sketch);
+        sketch_raw(e, r, first, last, e.sketch.raw_sketch);
+        sketch_minhash(e, r, e.sketch.raw_sketch, e.sketch.index_sketch);
       } else {
         const size_t vb = e.val64 ? 8 : 4;
-        unsigned char* av = e.foreign_val.get<unsigned char>((bound + 1) * vb);
-        u64* ao = e.foreign_org.get<u64>(bound + 1);
+        unsigned char* av = e.sketch.foreign_val.get<unsigned char>((bound + 1) * vb);
+        u64* ao = e.sketch.foreign_org.get<u64>(bound + 1);
         u64 n_acc = 0;
         for (size_t c = 0; c + 1 < cuts.size(); ++c) {
-          sketch_raw(e, r, cuts[c], cuts[c + 1], e.raw_sketch);
-          sketch_minhash(e, r, e.raw_sketch, e.index_sketch);
-          const u64 n = e.index_sketch.count;
+          sketch_raw(e, r, cuts[c], cuts[c + 1], e.sketch.raw_sketch);
+          sketch_minhash(e, r, e.sketch.raw_sketch, e.sketch.index_sketch);
+          const u64 n = e.sketch.index_sketch.count;
           if (n_acc + n > bound) throw HipError("[raven_hip] rvn_shard_sketch_range: more selected minimizers than len / k per read");
           if (n) {
-            RVN_HIP(hipMemcpyAsync(av + n_acc * vb, e.index_sketch.val.ptr, n * vb, hipMemcpyDeviceToDevice, e.stream));
-            RVN_HIP(hipMemcpyAsync(ao + n_acc, e.index_sketch.org.ptr, n * 8, hipMemcpyDeviceToDevice, e.stream));
+            RVN_HIP(hipMemcpyAsync(av + n_acc * vb, e.sketch.index_sketch.val.ptr, n * vb, hipMemcpyDeviceToDevice, e.stream));
+            RVN_HIP(hipMemcpyAsync(ao + n_acc, e.sketch.index_sketch.org.ptr, n * 8, hipMemcpyDeviceToDevice, e.stream));
           }
           n_acc += n;
         }
         RVN_HIP(rvn_stream_sync(e.stream));
-        e.index_sketch.val.swap(e.foreign_val);
-        e.index_sketch.org.swap(e.foreign_org);
-        e.index_sketch.first = first;
-        e.index_sketch.last = last;
-        e.index_sketch.count = n_acc;  // (read_off of the pieces is not kept: nothing downstream of a query-only sketch reads it)
+        e.sketch.index_sketch.val.swap(e.sketch.foreign_val);
+        e.sketch.index_sketch.org.swap(e.sketch.foreign_org);
+        e.sketch.index_sketch.first = first;
+        e.sketch.index_sketch.last = last;
+        e.sketch.index_sketch.count = n_acc;  // (read_off of the pieces is not kept: nothing downstream of a query-only sketch reads it)
       }
-      const u64 n = e.index_sketch.count;
+      const u64 n = e.sketch.index_sketch.count;
       if (n) {
-        or_flags_kernel<<<static_cast<u32>((n + 255) / 256), 256, 0, e.stream>>>(e.index_sketch.org.as<u64>(), n, kQueryFlag | kForeignFlag);
+        or_flags_kernel<<<static_cast<u32>((n + 255) / 256), 256, 0, e.stream>>>(e.sketch.index_sketch.org.as<u64>(), n, kQueryFlag | kForeignFlag);
         RVN_LAUNCH_CHECK();
       }
     } else if (index_minhash) {
-      sketch_raw(e, r, first, last, e.raw_sketch);
-      sketch_minhash(e, r, e.raw_sketch, e.index_sketch);
+      sketch_raw(e, r, first, last, e.sketch.raw_sketch);
+      sketch_minhash(e, r, e.sketch.raw_sketch, e.sketch.index_sketch);
     } else {
-      sketch_raw(e, r, first, last, e.raw_sketch);
-      e.join_query_count = sketch_flag_queries(e, r, e.raw_sketch);  // minhash-selected entries get kQueryFlag
+      sketch_raw(e, r, first, last, e.sketch.raw_sketch);
+      e.sketch.join_query_count = sketch_flag_queries(e, r, e.sketch.raw_sketch);  // minhash-selected entries get kQueryFlag
     }
     *count = res.count;
     if (!foreign)
@@ -140,7 +140,7 @@ int shard_sketch_fetch(rvn_engine* h, uint64_t* values, uint64_t* origins, hipMe
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    Sketch& s = e.shard_sketch_minhash ? e.index_sketch : e.raw_sketch;
+    Sketch& s = e.sketch.shard_sketch_minhash ? e.sketch.index_sketch : e.sketch.raw_sketch;
     RVN_HIP(hipSetDevice(e.device));
     if (kind == hipMemcpyDeviceToDevice) {
       if (s.count == 0) return RVN_OK;
@@ -160,7 +160,7 @@ int shard_sketch_fetch(rvn_engine* h, uint64_t* values, uint64_t* origins, hipMe
 int shard_index_build(rvn_engine* h, const uint64_t* values, const uint64_t* origins, uint64_t n, int all_query, uint64_t n_flagged,
                       hipMemcpyKind kind, const char* what) {
   return guarded(h, h && !(n && (!values || !origins)), what, [&](Engine& e) -> int {
-    Sketch& sk = e.index_sketch;
+    Sketch& sk = e.sketch.index_sketch;
     sk.first = 0;
     sk.last = 0;
     sk.count = n;
@@ -180,10 +180,10 @@ int shard_index_build(rvn_engine* h, const uint64_t* values, const uint64_t* ori
     if (n) put(e, dorg, origins, n * 8, kind);
     e.c_index_min += n;
     index_build(e, sk, false);
-    e.c_index_keys += e.index.u;
-    e.index.has_query_flags = !all_query;
-    e.index.all_query = all_query != 0;
-    e.join_query_count = all_query ? n : n_flagged;
+    e.c_index_keys += e.sketch.index.u;
+    e.sketch.index.has_query_flags = !all_query;
+    e.sketch.index.all_query = all_query != 0;
+    e.sketch.join_query_count = all_query ? n : n_flagged;
     RVN_HIP(rvn_stream_sync(e.stream));
     return RVN_OK;
   });
@@ -214,16 +214,16 @@ int rvn_shard_key_counts(rvn_engine* h, uint32_t* counts) {
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
-    const u64 u = e.index.u;
+    const u64 u = e.sketch.index.u;
     if (u == 0) return RVN_OK;
     if (!counts) return fail(RVN_EINVAL, "[raven_hip] rvn_shard_key_counts: NULL argument");
     RVN_HIP(hipSetDevice(e.device));
     std::vector<u32> st(u + 1);
-    RVN_HIP(hipMemcpy(st.data(), e.index.u_start.ptr, (u + 1) * 4, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(st.data(), e.sketch.index.u_start.ptr, (u + 1) * 4, hipMemcpyDeviceToHost));
     // (members only: query-only entries of reads outside the index batch, kForeignFlag, are the front of their run; a run
     // without members reports 0 and the caller drops it)
-    std::vector<u64> so(e.index.m);
-    if (e.index.m) RVN_HIP(hipMemcpy(so.data(), e.index.s_org[e.index.cur].ptr, e.index.m * 8, hipMemcpyDeviceToHost));
+    std::vector<u64> so(e.sketch.index.m);
+    if (e.sketch.index.m) RVN_HIP(hipMemcpy(so.data(), e.sketch.index.s_org[e.sketch.index.cur].ptr, e.sketch.index.m * 8, hipMemcpyDeviceToHost));
     for (u64 i = 0; i < u; ++i) counts[i] = st[i + 1] - st[i] - run_foreign_prefix(so.data(), st[i], st[i + 1] - st[i]);
     return RVN_OK;
   });
@@ -249,9 +249,9 @@ int rvn_shard_join(rvn_engine* h, uint32_t n_reads_total, int avoid_equal, int a
 int rvn_shard_join_range(rvn_engine* h, uint32_t n_reads_total, int avoid_equal, int avoid_symmetric, uint32_t query_first,
                          uint32_t query_last, uint64_t* n_matches) {
   return guarded(h, h && n_matches, "[raven_hip] rvn_shard_join: NULL argument", [&](Engine& e) -> int {
-    e.shard_join_reads = n_reads_total;
-    e.shard_join_matches = join_index_matches(e, n_reads_total, avoid_equal != 0, avoid_symmetric != 0, query_first, query_last);
-    *n_matches = e.shard_join_matches;
+    e.map.shard_join_reads = n_reads_total;
+    e.map.shard_join_matches = join_index_matches(e, n_reads_total, avoid_equal != 0, avoid_symmetric != 0, query_first, query_last);
+    *n_matches = e.map.shard_join_matches;
     RVN_HIP(rvn_stream_sync(e.stream));
     return RVN_OK;
   });
@@ -263,10 +263,10 @@ int shard_join_fetch(rvn_engine* h, uint64_t* grp, uint64_t* pos, uint64_t* seg_
     if (!h) return fail(RVN_EINVAL, "[raven_hip] NULL engine");
     Engine& e = h->e;
     RVN_HIP(hipSetDevice(e.device));
-    const u64 H = e.shard_join_matches;
-    if (H && grp) put(e, grp, e.m_grp[0].ptr, H * 8, kind);
-    if (H && pos) put(e, pos, e.m_pos[0].ptr, H * 8, kind);
-    if (seg_off) put(e, seg_off, e.seg_off.ptr, (static_cast<size_t>(e.shard_join_reads) + 1) * 8, kind);
+    const u64 H = e.map.shard_join_matches;
+    if (H && grp) put(e, grp, e.map.m_grp[0].ptr, H * 8, kind);
+    if (H && pos) put(e, pos, e.map.m_pos[0].ptr, H * 8, kind);
+    if (seg_off) put(e, seg_off, e.map.seg_off.ptr, (static_cast<size_t>(e.map.shard_join_reads) + 1) * 8, kind);
     if (kind == hipMemcpyDeviceToDevice) RVN_HIP(rvn_stream_sync(e.stream));
     return RVN_OK;
   });
@@ -281,17 +281,17 @@ int shard_chain(rvn_engine* h, const rvn_reads* own, const uint64_t* grp, const 
     const u32 nr = r.n;
     const u64 H = n_matches ? *n_matches : seg_off[nr];
     if (H && (!grp || !pos)) return fail(RVN_EINVAL, what + ": NULL matches");
-    u64* d_seg = e.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+    u64* d_seg = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
     put(e, d_seg, seg_off, (static_cast<size_t>(nr) + 1) * 8, kind);
-    u64* g0 = e.m_grp[0].get<u64>(H + 1);
-    u64* p0 = e.m_pos[0].get<u64>(H + 1);
-    e.m_grp[1].reserve((H + 1) * 8);
-    e.m_pos[1].reserve((H + 1) * 8);
+    u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
+    u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
+    e.map.m_grp[1].reserve((H + 1) * 8);
+    e.map.m_pos[1].reserve((H + 1) * 8);
     if (H) {
       put(e, g0, grp, H * 8, kind);
       put(e, p0, pos, H * 8, kind);
     }
-    MapOut& out = e.map_out;
+    MapOut& out = e.map.out;
     out.first = 0;
     out.last = nr;
     out.n_query = 0;

@@ -561,18 +561,18 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
   if (n_pairs == 0) return;
   hipStream_t s = e.stream;
   const EdPair* d_pairs = reinterpret_cast<const EdPair*>(d_pairs_raw);
-  u32* d_cnt = e.ed_cnt.get<u32>(kEdHistAt + kEdHistBins);
+  u32* d_cnt = e.ed.cnt.get<u32>(kEdHistAt + kEdHistBins);
   RVN_HIP(hipMemsetAsync(d_cnt, 0, (kEdHistAt + kEdHistBins) * 4, s));
   RVN_HIP(hipMemsetAsync(d_out, 0xFF, static_cast<size_t>(n_pairs) * 4, s));  // everything starts as "needs the wave kernel"
   // ---- stage 1: one lane per pair for narrow bands.  Tried on a sample first: it pays only when most pairs are
   // closer than ~384 edits (HiFi-like); for ONT-like spans nearly every pair would come back as overflow.
-  u32* d_sk = e.ed_sort.get<u32>(4 * static_cast<size_t>(n_pairs) + 8);
+  u32* d_sk = e.ed.sort.get<u32>(4 * static_cast<size_t>(n_pairs) + 8);
   u32* d_sk1 = d_sk + n_pairs + 1;
   u32* d_sv = d_sk1 + n_pairs + 1;
   u32* d_sv1 = d_sv + n_pairs + 1;
   ed_keys_kernel<<<div_up(n_pairs, 256), 256, 0, s>>>(d_pairs, n_pairs, d_sk, d_sv);
   RVN_LAUNCH_CHECK();
-  const int which = radix_sort_pairs_u32_u32(d_sk, d_sk1, d_sv, d_sv1, n_pairs, 32, e.sort_tmp, e.scan_tmp, s, kKPileSortUp,
+  const int which = radix_sort_pairs_u32_u32(d_sk, d_sk1, d_sv, d_sv1, n_pairs, 32, e.scratch.sort_tmp, e.scratch.scan_tmp, s, kKPileSortUp,
                                              kKPileSortDown);
   const u32* d_order = which ? d_sv1 : d_sv;
   const u32* d_sorted_keys = which ? d_sk1 : d_sk;
@@ -622,7 +622,7 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
     for (int c = kEdClasses - 1; c >= 1; --c) piece(h_cnt[kEdBoundsAt + c - 1], class_b[c]);
     piece(n_main, class_b[0]);
   }
-  u32* d_todo = e.ed_todo.get<u32>(static_cast<size_t>(n_pairs) + 1);
+  u32* d_todo = e.ed.todo.get<u32>(static_cast<size_t>(n_pairs) + 1);
   if (narrow_used) {  // second chance with the widest window for the pairs a narrower one lost
     RVN_HIP(hipMemsetAsync(d_cnt, 0, 4, s));
     ed_collect_overflow_kernel<<<div_up(n_pairs, 256), 256, 0, s>>>(d_out, n_pairs, false, d_todo, d_cnt);
@@ -658,8 +658,8 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
     hb_off.push_back(hb_total);
     hb_total += 2ULL * (static_cast<u64>(hp[i].b_len) + 1);
   }
-  u64* d_off = e.tmp_d.get<u64>(hb_off.size() + 1);
-  signed char* d_hb = e.tmp_f.get<signed char>(hb_total + 16);
+  u64* d_off = e.scratch.tmp_d.get<u64>(hb_off.size() + 1);
+  signed char* d_hb = e.scratch.tmp_f.get<signed char>(hb_total + 16);
   RVN_HIP(hipMemcpyAsync(d_todo, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, s));
   RVN_HIP(hipMemcpyAsync(d_off, hb_off.data(), hb_off.size() * 8, hipMemcpyHostToDevice, s));
   RVN_KLAUNCH(kKEditFull, ed_full_kernel<<<n_full, 64, 0, s>>>(r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, d_todo, n_full,
@@ -672,8 +672,8 @@ void edit_distance_batch(Engine& e, const ReadsDev& r, const u32* h_pairs, u32 n
                          double* kernel_ms, u64* cells) {
   if (n_pairs == 0) return;
   hipStream_t s = e.stream;
-  EdPair* d_pairs = e.tmp_a.get<EdPair>(static_cast<size_t>(n_pairs) + 1);
-  u32* d_out = e.tmp_b.get<u32>(static_cast<size_t>(n_pairs) + 1);
+  EdPair* d_pairs = e.scratch.tmp_a.get<EdPair>(static_cast<size_t>(n_pairs) + 1);
+  u32* d_out = e.scratch.tmp_b.get<u32>(static_cast<size_t>(n_pairs) + 1);
   RVN_HIP(hipMemcpyAsync(d_pairs, h_pairs, static_cast<size_t>(n_pairs) * sizeof(EdPair), hipMemcpyHostToDevice, s));
   RVN_HIP(hipEventRecord(e.ev0, s));
   edit_distance_dev(e, r, reinterpret_cast<const u32*>(d_pairs), n_pairs, d_out, nullptr);

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -19,6 +20,15 @@ constexpr int kMaxWindow = 256;    // largest supported winnowing window w
 inline u64 next_reads_serial() {
   static std::atomic<u64> counter{0};
   return ++counter;
+}
+
+// A struct that owns device buffers names them ONCE, in for_each_buf directly under their declarations; its release()
+// hands them back through that and resets every descriptor that speaks about their contents.  The engine's
+// scratch-release path and the byte count of its tests are loops over these, never a list of their own.
+using BufFn = std::function<void(DevBuf&)>;
+template <typename G>
+void release_bufs(G& g) {
+  g.for_each_buf([](DevBuf& b) { b.release(); });
 }
 
 struct ReadsDev {
@@ -53,6 +63,7 @@ struct Sketch {
   DevBuf val;       // V[count]   (u32 when 2k < 32, else u64)
   DevBuf org;       // u64[count] id << 32 | pos << 1 | strand
   DevBuf read_off;  // u32[last - first + 1]
+  void for_each_buf(const BufFn& f) { f(val), f(org), f(read_off); }
 };
 
 struct Index {
@@ -74,6 +85,9 @@ struct Index {
   bool has_query_flags = false;  // origins carry kQueryFlag
   bool all_query = false;        // every index entry is a query minimizer (index built with minhash)
   u32 first = 0, last = 0;       // read range the index was built from
+  void for_each_buf(const BufFn& f) {
+    f(s_val[0]), f(s_val[1]), f(s_org[0]), f(s_org[1]), f(u_val), f(u_start), f(table), f(direct);
+  }
 };
 
 struct MapOut {
@@ -90,6 +104,7 @@ struct MapOut {
   DevBuf anchors;      // u64[n_matches] (sparse: regions of the emitting intervals)
   DevBuf anchor_off;   // u64[n_overlaps] index of an overlap's first anchor in `anchors`
   DevBuf anchor_cnt;   // u32[n_overlaps]
+  void for_each_buf(const BufFn& f) { f(ovl), f(ovl_read_off), f(filtered), f(anchors), f(anchor_off), f(anchor_cnt); }
 };
 
 struct StageTimes {
@@ -131,157 +146,24 @@ struct EngineOptions {
 const char* engine_option_names();   // comma-separated, for the error message
 long long* engine_option(EngineOptions& o, const char* name);
 
-struct Engine {
-  EngineOptions opt;
-  // Every C-ABI entry point that touches the engine's state (scratch buffers, stream, last Map result) holds this
-  // lock for its whole duration: ram::MinimizerEngine::Map is const and called concurrently from Raven's pool workers
-  // (RavenLib/src/construct.cc:60-64, :373-381), so the boundary has to be safe under concurrent callers.
-  std::recursive_mutex mu;
-  u32 k, w, bandwidth, chain, matches, gap;
-  int device = 0;
-  bool val64 = false;  // true when minimizer values need 64 bits
-  hipStream_t stream = nullptr;
-  Index index;
-  Sketch index_sketch, query_sketch, raw_sketch;
-  // query sketch prepared ahead of map_batch (valid for exactly this range / minhash flag)
-  bool query_ready = false;
-  u32 query_ready_first = 0, query_ready_last = 0;
-  bool query_ready_minhash = false;
-  u64 join_query_count = 0;  // number of query minimizers flagged in the index (self-join path)
-  bool shard_sketch_minhash = false;           // which sketch rvn_shard_sketch left its result in
-  u32 shard_join_reads = 0;                    // rvn_shard_join: segments of the last join
-  u64 shard_join_matches = 0;
-  MapOut map_out;
-  // scratch
+struct Engine;
+
+// Scratch every stage may use between two of its own launches; nothing in it outlives the call that filled it
+struct SharedScratch {
   DevBuf tmp_a, tmp_b, tmp_c, tmp_d, tmp_e, tmp_f, scan_tmp, sort_tmp;
-  DevBuf sh_hist, sh_off, sh_ptrs;  // shard.hip: tile histograms / offsets / pointer tables of the partition steps
-  DevBuf q_start, q_cnt, m_off;
-  // the reads' sketch of a polishing round's mapping, kept for the next round (the reads do not change between rounds; only
-  // the targets do): per read batch, for ONE read set at a time (`owner` = ReadsDev::serial)
-  struct PolishSketch {
-    u32 first = 0, last = 0;
-    Sketch sk;
-  };
-  u64 polish_sketch_owner = 0;
-  std::vector<std::unique_ptr<PolishSketch>> polish_sketches;
-  DevBuf pl_tval, pl_torg;          // the targets' minimizers of a polishing round, appended to every read batch's (polish.hip)
-  DevBuf foreign_val, foreign_org;  // a query-only sketch appended from its pieces (rvn_shard_sketch_range)
-  DevBuf sketch_sum;  // 64-bit total of a sketch whose 32-bit offsets could wrap (sketch.hip)
-  DevBuf m_grp[2], m_pos[2];
-  DevBuf seg_off, iv_slot_begin, iv_slot_end, iv_cnt, iv_off, iv_begin, iv_end;
-  DevBuf lis_min, lis_pred, lis_tail, lis_mask, ovl_slots, ovl_flags, ovl_scan, chain_big;
-  DevBuf poa_scratch, poa2_scratch, polish_quals;
-  DevBuf ed_cnt, ed_sort, ed_todo;
-  // second pass / identity filters (pass2.hip)
-  DevBuf p2_slot, p2_pairs, p2_dist, p2_regions, p2_index_of, p2_kmers_off, p2_ok, p2_keep, p2_tmp_ovl;
-  DevBuf io_text[2];  // input path: the file's text in HBM (io.hip)
-  int stage_kind = 0;   // the stage entry point running (engine_release_scratch_if_tight)
-  u32 oom_mask = 0;     // kinds of stages that ran out of device memory once: they start from released scratch
-  std::vector<std::pair<std::unique_ptr<PinBuf>, bool>> io_pin;  // its page-locked slabs (buffer, handed out)
-  DevBuf poa_sched, poa_redo_w, poa_redo_i;  // LPT order / escalation lists of a POA batch (poa_run_dev)
-  // alignment-path stage of a polishing round (nwpath.hip): stored band words + scores, jobs, results
-  DevBuf nw_hs, nw_ck, nw_hs2, nw_ck2, nw_hs3, nw_ck3, nw_hs4, nw_ck4, nw_strip, nw_jobs, nw_res;  // alignment paths: horizontal-delta streams, checkpoints, jobs, results
-  double nw_rate = -1.0;  // running estimate of edit distance / length of the read-to-target alignments (< 0: unknown)
-  // polishing front end (polish.hip): best overlaps, window records, layer tables, consensus
-  DevBuf pl_best, pl_best_t, pl_idmap, pl_recs, pl_keep, pl_win_cnt, pl_win_off, pl_win_fill, pl_win_meta, pl_first_window,
-      pl_keys, pl_lays_tmp, pl_lays, pl_wins, pl_out, pl_len, pl_status, pl_ok, pl_cons_off, pl_final, pl_qual_off, pl_misc;
-  // the last COMPLETE polishing round's stitched consensus is still in pl_final: byte offsets of the targets' sequences there
-  // (rvn_polish_output_as_reads: the next round's targets without the way over the host)
-  std::vector<u64> pl_last_off;
-  bool pl_last_valid = false;
-  std::vector<u32> polish_target_reads;  // reads used per target in the last polishing round
-  // best-overlap table for the NEXT polishing round (rvn_polish_set_best; consumed by that round)
-  std::vector<Overlap> polish_given_best;
-  std::vector<u32> polish_given_best_t;
-  bool polish_given_valid = false;
-  // layer table of the last polishing round (still in pl_wins / pl_lays / pl_ok), for rvn_polish_fetch_layers
-  u32 polish_last_windows = 0;
-  u64 polish_last_layers = 0, polish_last_w0 = 0;
-  bool polish_last_has_ok = false;
-  std::vector<u64> polish_last_read_off;
-  int poa_mode = 0;  // 0 banded 32 (poa4.hip) -> 64 -> 128 -> 256 (poa2.hip) -> full matrix; 1 full matrix only; 2 / 3 / 4 band 64 / 128 / 256 only (tests); 9 poa4.hip only (band 32, rows on lanes)
-  u32 poa_fallback_windows = 0;  // windows of the last batch that needed more than the 128-column band
-  u32 poa_fullmatrix_windows = 0;  // ... of which re-run by the full-matrix kernel
-  u32 poa_wide_windows = 0;      // windows of the last batch re-run with the 128-column band
-  u32 poa_narrow_windows = 0;    // windows of the 32-column first attempt (poa4.hip) re-run with the 64-column band
-  DevBuf anc_slot_off, anc_slot_cnt;
-  bool keep_anchors = false;  // map_batch also returns the chain anchors of every overlap
-  unsigned long long poa_phase_cycles[8] = {};  // subgraph, dp, traceback, add, order, consensus (last call); [6], [7]: DP cells
-  // DP cells of the banded POA kernel since the last reset_stats: full-matrix equivalent (graph rows x layer length of
-  // every layer alignment: what spoa computes) / inside the computed band; number of batches
-  u64 poa_cells_full = 0, poa_cells_band = 0, poa_calls = 0;
-  StageTimes times;
-  KernelTimers ktimers;
-  // counters for algorithmic bytes (SURVEY §8(d))
-  u64 c_index_bases = 0, c_index_min = 0, c_index_keys = 0, c_query_bases = 0, c_query_min = 0, c_matches = 0,
-      c_overlaps = 0;
-  u64 c_intervals = 0;
-  bool timing = true;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipStream_t nw_streams[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // alignment-path stage: [0..3] walk streams (beside the sweeps), one per buffer set; [4] uploads of a pass planned while another one sweeps
-  hipEvent_t nw_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [0..3] the walk of a buffer set is done, [4] sweep -> walk
-  hipStream_t nw_side[3] = {nullptr, nullptr, nullptr};  // ... sweep launches of few waves (the pilot's, the several-blocks-per-lane variants of the longest alignments) beside the main stream's
-  hipEvent_t nw_side_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [0..2] the side stream's sweeps are done, [3] main -> side
-  u64* h_pin = nullptr;  // pinned host scratch for small device->host size read-backs
-  PinBuf pin_big;        // pinned staging for bulk read-backs up to 256 MB (polishing: chain anchors)
-  HostBuf host_big;      // ... and the unpinned one for larger ones
-  PinBuf pin_out;        // pinned consensus buffer of the POA chunk in flight
-  u64 polish_chunk_windows = 16384;  // windows per POA chunk of a polishing round (0 = everything in one batch)
-  PileState* pile_pool = nullptr;  // buffers of the last destroyed pass, adopted by the next one (rvn_pass1 below)
-  std::shared_ptr<int> life = std::make_shared<int>(0);  // lets handles notice that their engine is gone
-};
-
-// The per-site kernel timers of the engine count the launches of the entry point that holds one of these
-struct UseTimers {
-  explicit UseTimers(Engine& e) {
-    e.ktimers.stream = e.stream;
-    // Fold the event pairs of the previous entry point into the per-site sums now (the stream is idle between entry
-    // points): the events are reused instead of growing the pool by two hipEventCreate per launch, which cost more
-    // than the launches themselves on a slow host (0.5 s per pass at C4).
-    if (e.ktimers.enabled && !e.ktimers.recs.empty()) {
-      (void)rvn_stream_sync(e.stream);
-      e.ktimers.resolve();
-    }
-    g_kernel_timers = &e.ktimers;
+  void for_each_buf(const BufFn& f) {
+    f(tmp_a), f(tmp_b), f(tmp_c), f(tmp_d), f(tmp_e), f(tmp_f), f(scan_tmp), f(sort_tmp);
   }
-  ~UseTimers() { g_kernel_timers = nullptr; }
-};
-
-// Hands every scratch / intermediate buffer of the engine back to the allocator (index, sketches, last Map result,
-// stage scratch).  Buffers only ever grow, so a stage with a very different footprint (HiFi first pass -> polishing)
-// can otherwise find the HBM full of the previous stage's scratch.  Only valid between stages: nothing of the
-// released state may be needed afterwards (every stage entry point rebuilds what it uses).
-void engine_release_scratch(Engine& e);
-// ... when less than a third of the device memory is free (called at stage entry points)
-void engine_release_scratch_if_tight(Engine& e, int stage_kind);  // kind: 0 pass 1, 1 pass 2, 2 polishing round, 3 polishing map
-
-// Reads one 4- or 8-byte value from the device through pinned memory (stream-ordered, then synchronises).
-inline u64 read_back(Engine& e, const void* dptr, size_t bytes) {
-  e.h_pin[0] = 0;
-  RVN_HIP(hipMemcpyAsync(e.h_pin, dptr, bytes, hipMemcpyDeviceToHost, e.stream));
-  RVN_HIP(rvn_stream_sync(e.stream));
-  return e.h_pin[0];
-}
-
-// Stage timing helper: records HIP events on the engine stream around a stage.
-struct StageTimer {
-  Engine& e;
-  int stage;
-  StageTimer(Engine& eng, int st) : e(eng), stage(st) {
-    if (e.timing) RVN_HIP(hipEventRecord(e.ev0, e.stream));
-  }
-  void stop() {
-    if (!e.timing) return;
-    RVN_HIP(hipEventRecord(e.ev1, e.stream));
-    RVN_HIP(hipEventSynchronize(e.ev1));
-    float ms = 0;
-    RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
-    e.times.ms[stage] += ms;
-    e.times.launches[stage] += 1;
-  }
+  void release() { release_bufs(*this); }
 };
 
 // input path (io.hip)
+struct IoState {
+  DevBuf text[2];  // the file's text in HBM
+  std::vector<std::pair<std::unique_ptr<PinBuf>, bool>> pin;  // its page-locked slabs (buffer, handed out): host memory, kept
+  void for_each_buf(const BufFn& f) { f(text[0]), f(text[1]); }
+  void release() { release_bufs(*this); }
+};
 struct LoadStats {
   u64 n_sequences = 0, n_bases = 0;
   int has_quality = 0;
@@ -292,6 +174,58 @@ struct LoadStats {
 void reads_load(Engine& e, const std::string& path, ReadsDev& R, std::vector<std::string>& names, LoadStats& st);
 
 // ---- stages (one translation unit each) -------------------------------------
+// sketches and the index (sketch.hip, index.hip; abi_shard.hip for the sharded pass)
+struct SketchState {
+  Index index;
+  Sketch index_sketch, query_sketch, raw_sketch;
+  struct QueryReady {  // query_sketch was prepared ahead of map_batch, for exactly this range / minhash flag
+    bool valid = false;
+    u32 first = 0, last = 0;
+    bool minhash = false;
+  } query_ready;
+  u64 join_query_count = 0;           // number of query minimizers flagged in the index (self-join path)
+  bool shard_sketch_minhash = false;  // which sketch rvn_shard_sketch left its result in
+  DevBuf foreign_val, foreign_org;    // a query-only sketch appended from its pieces (rvn_shard_sketch_range)
+  DevBuf sum;  // 64-bit total of a sketch whose 32-bit offsets could wrap (sketch.hip)
+  void for_each_buf(const BufFn& f) {
+    index.for_each_buf(f), index_sketch.for_each_buf(f), query_sketch.for_each_buf(f), raw_sketch.for_each_buf(f);
+    f(foreign_val), f(foreign_org), f(sum);
+  }
+  void release() {
+    release_bufs(*this);
+    index.m = index.u = 0;
+    index.table_built = index.direct_built = false;
+    index_sketch.count = query_sketch.count = raw_sketch.count = join_query_count = 0;
+    query_ready = {};
+  }
+};
+// Map (map.hip): the last result and the scratch of the match / chain stages
+struct MapState {
+  MapOut out;
+  DevBuf q_start, q_cnt, m_off;
+  DevBuf m_grp[2], m_pos[2];
+  DevBuf seg_off, iv_slot_begin, iv_slot_end, iv_cnt, iv_off, iv_begin, iv_end;
+  DevBuf lis_min, lis_pred, lis_tail, lis_mask, ovl_slots, ovl_flags, ovl_scan, chain_big;
+  DevBuf anc_slot_off, anc_slot_cnt;
+  bool keep_anchors = false;  // map_batch also returns the chain anchors of every overlap
+  u32 shard_join_reads = 0;   // rvn_shard_join: segments of the last join (in seg_off / m_grp[0] / m_pos[0])
+  u64 shard_join_matches = 0;
+  void for_each_buf(const BufFn& f) {
+    out.for_each_buf(f);
+    f(q_start), f(q_cnt), f(m_off), f(m_grp[0]), f(m_grp[1]), f(m_pos[0]), f(m_pos[1]);
+    f(seg_off), f(iv_slot_begin), f(iv_slot_end), f(iv_cnt), f(iv_off), f(iv_begin), f(iv_end);
+    f(lis_min), f(lis_pred), f(lis_tail), f(lis_mask), f(ovl_slots), f(ovl_flags), f(ovl_scan), f(chain_big);
+    f(anc_slot_off), f(anc_slot_cnt);
+  }
+  void release() {
+    release_bufs(*this);
+    out.first = out.last = 0;
+    out.n_query = out.n_matches = out.n_intervals = out.n_overlaps = 0;
+    out.has_anchors = false;
+    shard_join_reads = 0;
+    shard_join_matches = 0;
+  }
+};
 void reads_build_tiles(Engine& e, ReadsDev& r);
 // 2-bit packing of one-byte codes already in HBM: read i = codes[base_off[i] ..), words at word_off[i] (sketch.hip)
 void pack_codes_on_device(Engine& e, const u8* d_codes, const u64* d_base_off, const u64* d_word_off, u32 n_reads,
@@ -303,24 +237,45 @@ void index_build(Engine& e, Sketch& sk, bool build_table = true);  // consumes s
 void index_build_table(Engine& e);                               // lazy: distinct keys + direct-address table
 // minhash-select on a raw sketch, marking the selected minimizers with kQueryFlag in raw.org; returns their count
 u64 sketch_flag_queries(Engine& e, const ReadsDev& r, Sketch& raw);
-void index_filter(Engine& e, double freq);               // sets e.index.occurrence
+void index_filter(Engine& e, double freq);               // sets e.sketch.index.occurrence
 void index_key_histogram(Engine& e, std::vector<u64>& hist, std::vector<u32>& over);  // count-of-counts (65536 bins)
 void map_batch(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoid_equal, bool avoid_symmetric,
                bool minhash, bool want_filtered, MapOut& out);
 
-// self-join of the index for global query ids 0..n_reads-1 -> e.m_grp[0] / e.m_pos[0] / e.seg_off (map.hip)
+// self-join of the index for global query ids 0..n_reads-1 -> e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (map.hip)
 void map_batch_query_only(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 n_query, MapOut& out);
 u64 join_index_matches(Engine& e, u32 n_reads, bool avoid_equal, bool avoid_symmetric, u32 q_lo = 0,
                        u32 q_hi = 0xFFFFFFFFu);  // only query reads with q_lo <= id < q_hi
-// chain stage of Map on matches already in e.m_grp[0] / e.m_pos[0] / e.seg_off (map.hip)
+// chain stage of Map on matches already in e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (map.hip)
 void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, MapOut& out);
 
+struct EditDistanceState {
+  DevBuf cnt, sort, todo;
+  void for_each_buf(const BufFn& f) { f(cnt), f(sort), f(todo); }
+  void release() { release_bufs(*this); }
+};
 // Batched exact edit distance (edit_distance.hip). h_pairs: n_pairs x {a_idx,a_begin,a_len,b_idx,b_begin,b_len,strand,0}
 void edit_distance_batch(Engine& e, const ReadsDev& r, const u32* h_pairs, u32 n_pairs, u32* h_out, double* kernel_ms,
                          u64* cells);
 // the same with pairs and distances resident in HBM (pass2.hip: identity filters)
 void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs, u32 n_pairs, u32* d_out, const u32* d_kmax = nullptr);
 
+// window consensus (poa.hip): scratch of a batch, which kernels run (tests), and what the last batch / all batches did
+struct PoaState {
+  DevBuf scratch, scratch2;
+  DevBuf sched, redo_w, redo_i;  // LPT order / escalation lists of a POA batch (poa_run_dev)
+  int mode = 0;  // 0 banded 32 (poa4.hip) -> 64 -> 128 -> 256 (poa2.hip) -> full matrix; 1 full matrix only; 2 / 3 / 4 band 64 / 128 / 256 only (tests); 9 poa4.hip only (band 32, rows on lanes)
+  u32 fallback_windows = 0;    // windows of the last batch that needed more than the 128-column band
+  u32 fullmatrix_windows = 0;  // ... of which re-run by the full-matrix kernel
+  u32 wide_windows = 0;        // windows of the last batch re-run with the 128-column band
+  u32 narrow_windows = 0;      // windows of the 32-column first attempt (poa4.hip) re-run with the 64-column band
+  unsigned long long phase_cycles[8] = {};  // subgraph, dp, traceback, add, order, consensus (last call); [6], [7]: DP cells
+  // DP cells of the banded POA kernel since the last reset_stats: full-matrix equivalent (graph rows x layer length of
+  // every layer alignment: what spoa computes) / inside the computed band; number of batches
+  u64 cells_full = 0, cells_band = 0, calls = 0;
+  void for_each_buf(const BufFn& f) { f(scratch), f(scratch2), f(sched), f(redo_w), f(redo_i); }
+  void release() { release_bufs(*this); }
+};
 // Batched POA window consensus (poa.hip); all arrays are host pointers, see rvn_poa_consensus_batch
 void poa_consensus_batch(Engine& e, const u8* h_codes, const u8* h_quals, const u64* h_layer_off, const u32* h_begins,
                          const u32* h_ends, const u32* h_has_qual, const u32* h_win_off, u32 n_windows, int m, int n,
@@ -342,6 +297,27 @@ struct PolishStats {
 };
 
 // alignment-path stage (nwpath.hip)
+struct NwState {
+  struct Set {
+    DevBuf hs, ck;  // stored band words (horizontal-delta streams), checkpoints
+  } sets[4];        // a sweep fills one while the walks of the others run
+  DevBuf strip, jobs, res;
+  double rate = -1.0;  // running estimate of edit distance / length of the read-to-target alignments (< 0: unknown); learned,
+                       // not a description of a buffer: it survives release()
+  // created together on the first use (open), destroyed with the engine
+  hipStream_t streams[5] = {};  // [0..3] walk streams (beside the sweeps), one per buffer set; [4] uploads of a pass planned while another one sweeps
+  hipEvent_t ev[5] = {};        // [0..3] the walk of a buffer set is done, [4] sweep -> walk
+  hipStream_t side[3] = {};     // sweep launches of few waves (the pilot's, the several-blocks-per-lane variants of the longest alignments) beside the main stream's
+  hipEvent_t side_ev[4] = {};   // [0..2] the side stream's sweeps are done, [3] main -> side
+  void for_each_buf(const BufFn& f) {
+    for (Set& s : sets) f(s.hs), f(s.ck);
+    f(strip), f(jobs), f(res);
+  }
+  void release() { release_bufs(*this); }
+  void open();   // all streams and events, or none and the error
+  void close();
+  ~NwState() { close(); }
+};
 struct NwJob;
 struct NwWindowRec;
 struct NwStats {
@@ -373,6 +349,11 @@ void nw_paths_expand(Engine& e, const NwPaths& p, u8* d_ops);
 int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r_len, u32 t_begin, u32 n, u32 q_begin, u32 m,
                         int rc, u32 w, u32 k, int force_R, NwWindowRec* recs, u32* distance, u32* band);
 // shard.hip — partition / regroup steps of the sharded pass, all pointers device pointers unless noted
+struct ShardState {
+  DevBuf hist, off, ptrs;  // tile histograms / offsets / pointer tables of the partition steps
+  void for_each_buf(const BufFn& f) { f(hist), f(off), f(ptrs); }
+  void release() { release_bufs(*this); }
+};
 void shard_split_minimizers(Engine& e, const u64* d_val, const u64* d_org, u64 n, u32 world, u64* d_val_out, u64* d_org_out,
                             u64* counts /* host [world] */);
 void shard_split_overlaps(Engine& e, const Overlap* d_ovl, u64 n, const u32* bounds /* host [world + 1] */, u32 world, u32 self,
@@ -390,6 +371,51 @@ struct PolishDirectOut {
   const u64* off;
   u64* len;
 };
+// What a polishing round keeps in the engine (polish.hip; read by abi_polish.hip and abi_reads.hip)
+struct PolishState {
+  // front end: best overlaps, window records, layer tables, consensus
+  DevBuf best, best_t, idmap, recs, keep, win_cnt, win_off, win_fill, win_meta, first_window, keys, lays_tmp, lays, wins, out,
+      len, status, ok, cons_off, stitched, quals, qual_off, misc;
+  DevBuf tval, torg;  // the targets' minimizers of the round, appended to every read batch's
+  // the reads' sketch of a round's mapping, kept for the next round (the reads do not change between rounds; only the
+  // targets do): per read batch, for ONE read set at a time (sketch_owner = ReadsDev::serial)
+  struct KeptSketch {
+    u32 first = 0, last = 0;
+    Sketch sk;
+  };
+  u64 sketch_owner = 0;
+  std::vector<std::unique_ptr<KeptSketch>> sketches;
+  // The two results a round leaves resident.  polish_round empties a record BEFORE the first write to its buffers and
+  // fills it when they are complete: a round that fails in between leaves no record, never the last one over new bytes.
+  struct LastLayers {  // the layer table in wins / lays / ok (rvn_polish_fetch_layers)
+    u32 windows = 0;
+    u64 layers = 0, w0 = 0;
+    bool has_ok = false;
+    std::vector<u64> read_off;
+  } last_layers;
+  struct LastConsensus {  // the stitched consensus of a round over every window: target t at stitched + off[t]
+    std::vector<u64> off;  // (rvn_polish_output_as_reads: the next round's targets without the way over the host)
+    bool valid = false;
+  } last_cons;
+  std::vector<u32> target_reads;  // reads used per target in the last round
+  // best-overlap table for the NEXT round (rvn_polish_set_best; consumed by that round)
+  std::vector<Overlap> given_best;
+  std::vector<u32> given_best_t;
+  bool given_valid = false;
+  void for_each_buf(const BufFn& f) {
+    f(best), f(best_t), f(idmap), f(recs), f(keep), f(win_cnt), f(win_off), f(win_fill), f(win_meta), f(first_window), f(keys);
+    f(lays_tmp), f(lays), f(wins), f(out), f(len), f(status), f(ok), f(cons_off), f(stitched), f(quals), f(qual_off), f(misc);
+    f(tval), f(torg);
+    for (auto& c : sketches) c->sk.for_each_buf(f);
+  }
+  void release() {
+    release_bufs(*this);
+    sketches.clear();  // (derived data, recomputed when needed)
+    sketch_owner = 0;
+    last_layers = {};
+    last_cons = {};
+  }
+};
 void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_last, double err_thr,
                      std::vector<Overlap>& best, std::vector<u32>& best_t, u64* n_overlaps);
 void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const u64* h_qual_off, double q_thr,
@@ -398,6 +424,14 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
                   std::vector<u32>* win_count = nullptr, std::vector<u32>* win_polished = nullptr,
                   const PolishDirectOut* direct = nullptr);
 
+// scratch of the second pass / identity filters (pass2.hip)
+struct Pass2Scratch {
+  DevBuf slot, pairs, dist, regions, index_of, kmers_off, ok, keep, tmp_ovl;
+  void for_each_buf(const BufFn& f) {
+    f(slot), f(pairs), f(dist), f(regions), f(index_of), f(kmers_off), f(ok), f(keep), f(tmp_ovl);
+  }
+  void release() { release_bufs(*this); }
+};
 // Result of the second mapping pass (pass2.hip), resident in HBM
 struct Pass2State {
   u32 n = 0;
@@ -555,6 +589,101 @@ struct LayoutStats {
 };
 void layout_force_directed(Engine& e, u32 n_components, const u32* h_off, const double* h_xy, const u64* h_adj_off,
                            const u32* h_adj, u32 n_iterations, double* h_xy_out, LayoutStats& st);
+
+// ---- the engine: parameters, stream, and one state group per stage, each released by its owner's release() ----
+struct Engine {
+  EngineOptions opt;
+  // Every C-ABI entry point that touches the engine's state (scratch buffers, stream, last Map result) holds this
+  // lock for its whole duration: ram::MinimizerEngine::Map is const and called concurrently from Raven's pool workers
+  // (RavenLib/src/construct.cc:60-64, :373-381), so the boundary has to be safe under concurrent callers.
+  std::recursive_mutex mu;
+  u32 k, w, bandwidth, chain, matches, gap;
+  int device = 0;
+  bool val64 = false;  // true when minimizer values need 64 bits
+  hipStream_t stream = nullptr;
+  SketchState sketch;
+  MapState map;
+  ShardState shard;
+  EditDistanceState ed;
+  Pass2Scratch p2;
+  PoaState poa;
+  NwState nw;
+  PolishState polish;
+  IoState io;
+  SharedScratch scratch;
+  // every group that owns device buffers (what engine_release_scratch releases)
+  template <typename F>
+  void for_each_group(F&& f) {
+    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(scratch);
+  }
+  int stage_kind = 0;   // the stage entry point running (engine_release_scratch_if_tight)
+  u32 oom_mask = 0;     // kinds of stages that ran out of device memory once: they start from released scratch
+  StageTimes times;
+  KernelTimers ktimers;
+  // counters for algorithmic bytes (SURVEY §8(d))
+  u64 c_index_bases = 0, c_index_min = 0, c_index_keys = 0, c_query_bases = 0, c_query_min = 0, c_matches = 0,
+      c_overlaps = 0;
+  u64 c_intervals = 0;
+  bool timing = true;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  u64* h_pin = nullptr;  // pinned host scratch for small device->host size read-backs
+  PinBuf pin_big;        // pinned staging for bulk read-backs up to 256 MB (polishing: chain anchors)
+  HostBuf host_big;      // ... and the unpinned one for larger ones
+  PinBuf pin_out;        // pinned consensus buffer of the POA chunk in flight
+  u64 polish_chunk_windows = 16384;  // windows per POA chunk of a polishing round (0 = everything in one batch)
+  PileState* pile_pool = nullptr;  // buffers of the last destroyed pass, adopted by the next one (rvn_pass1 below)
+  std::shared_ptr<int> life = std::make_shared<int>(0);  // lets handles notice that their engine is gone
+};
+
+// The per-site kernel timers of the engine count the launches of the entry point that holds one of these
+struct UseTimers {
+  explicit UseTimers(Engine& e) {
+    e.ktimers.stream = e.stream;
+    // Fold the event pairs of the previous entry point into the per-site sums now (the stream is idle between entry
+    // points): the events are reused instead of growing the pool by two hipEventCreate per launch, which cost more
+    // than the launches themselves on a slow host (0.5 s per pass at C4).
+    if (e.ktimers.enabled && !e.ktimers.recs.empty()) {
+      (void)rvn_stream_sync(e.stream);
+      e.ktimers.resolve();
+    }
+    g_kernel_timers = &e.ktimers;
+  }
+  ~UseTimers() { g_kernel_timers = nullptr; }
+};
+
+// Hands every scratch / intermediate buffer of the engine back to the allocator: every group's release(), then the pile
+// pool.  Buffers only ever grow, so a stage with a very different footprint (HiFi first pass -> polishing)
+// can otherwise find the HBM full of the previous stage's scratch.  Only valid between stages: nothing of the
+// released state may be needed afterwards (every stage entry point rebuilds what it uses).
+void engine_release_scratch(Engine& e);
+// ... when less than a quarter of the device memory is free (called at stage entry points)
+void engine_release_scratch_if_tight(Engine& e, int stage_kind);  // kind: 0 pass 1, 1 pass 2, 2 polishing round, 3 polishing map
+
+// Reads one 4- or 8-byte value from the device through pinned memory (stream-ordered, then synchronises).
+inline u64 read_back(Engine& e, const void* dptr, size_t bytes) {
+  e.h_pin[0] = 0;
+  RVN_HIP(hipMemcpyAsync(e.h_pin, dptr, bytes, hipMemcpyDeviceToHost, e.stream));
+  RVN_HIP(rvn_stream_sync(e.stream));
+  return e.h_pin[0];
+}
+
+// Stage timing helper: records HIP events on the engine stream around a stage.
+struct StageTimer {
+  Engine& e;
+  int stage;
+  StageTimer(Engine& eng, int st) : e(eng), stage(st) {
+    if (e.timing) RVN_HIP(hipEventRecord(e.ev0, e.stream));
+  }
+  void stop() {
+    if (!e.timing) return;
+    RVN_HIP(hipEventRecord(e.ev1, e.stream));
+    RVN_HIP(hipEventSynchronize(e.ev1));
+    float ms = 0;
+    RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
+    e.times.ms[stage] += ms;
+    e.times.launches[stage] += 1;
+  }
+};
 
 }  // namespace rvn
 

@@ -31,37 +31,34 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
   bool raw_handed_over = false;
   {
     StageTimer t(e, StageTimes::kSketch);
-    e.query_ready = false;
-    Index& ix = e.index;
+    e.sketch.query_ready = {};
+    Index& ix = e.sketch.index;
     ix.has_query_flags = false;
     ix.all_query = false;
-    sketch_raw(e, r, first, last, e.raw_sketch);
+    sketch_raw(e, r, first, last, e.sketch.raw_sketch);
     const bool join = prefetch_query && r.ids_are_indices;  // map_batch will self-join instead of probing
     if (join && !minhash) {
-      e.join_query_count = sketch_flag_queries(e, r, e.raw_sketch);
+      e.sketch.join_query_count = sketch_flag_queries(e, r, e.sketch.raw_sketch);
       ix.has_query_flags = true;
     } else if (prefetch_query && !join) {
-      sketch_minhash(e, r, e.raw_sketch, e.query_sketch);
-      e.query_ready = true;
-      e.query_ready_first = first;
-      e.query_ready_last = last;
-      e.query_ready_minhash = true;
+      sketch_minhash(e, r, e.sketch.raw_sketch, e.sketch.query_sketch);
+      e.sketch.query_ready = {true, first, last, true};
     }
-    Sketch& is = e.index_sketch;
+    Sketch& is = e.sketch.index_sketch;
     if (join && minhash) {
-      sketch_minhash(e, r, e.raw_sketch, is);
+      sketch_minhash(e, r, e.sketch.raw_sketch, is);
       ix.all_query = true;
     } else if (!minhash) {
-      is.val.swap(e.raw_sketch.val);
-      is.org.swap(e.raw_sketch.org);
-      is.read_off.swap(e.raw_sketch.read_off);
+      is.val.swap(e.sketch.raw_sketch.val);
+      is.org.swap(e.sketch.raw_sketch.org);
+      is.read_off.swap(e.sketch.raw_sketch.read_off);
       is.first = first;
       is.last = last;
-      is.count = e.raw_sketch.count;
-      e.raw_sketch.count = 0;
+      is.count = e.sketch.raw_sketch.count;
+      e.sketch.raw_sketch.count = 0;
       raw_handed_over = true;
     } else if (prefetch_query) {
-      const Sketch& qs = e.query_sketch;
+      const Sketch& qs = e.sketch.query_sketch;
       const size_t vb = e.val64 ? 8 : 4;
       is.first = first;
       is.last = last;
@@ -73,20 +70,20 @@ void engine_minimize(Engine& e, const ReadsDev& r, u32 first, u32 last, bool min
         RVN_HIP(hipMemcpyAsync(is.org.ptr, qs.org.ptr, qs.count * 8, hipMemcpyDeviceToDevice, e.stream));
       }
     } else {
-      sketch_minhash(e, r, e.raw_sketch, is);
+      sketch_minhash(e, r, e.sketch.raw_sketch, is);
     }
     t.stop();
   }
   for (u32 i = first; i < last; ++i) e.c_index_bases += r.h_len[i];
-  e.c_index_min += e.index_sketch.count;
-  index_build(e, e.index_sketch, !(e.index.has_query_flags || e.index.all_query));
-  e.c_index_keys += e.index.u;
+  e.c_index_min += e.sketch.index_sketch.count;
+  index_build(e, e.sketch.index_sketch, !(e.sketch.index.has_query_flags || e.sketch.index.all_query));
+  e.c_index_keys += e.sketch.index.u;
   // index_build adopted the sketch's buffers and left the ones it displaced in index_sketch: they go back to the raw
   // sketch, so that TWO sets circulate (raw sketch <-> index side 0) and the second pass already finds its buffers —
   // left alone, three sets rotate through the three owners and every one of them is grown once (0.5 s at C4).
   if (raw_handed_over) {
-    if (e.raw_sketch.val.cap < e.index_sketch.val.cap) e.raw_sketch.val.swap(e.index_sketch.val);
-    if (e.raw_sketch.org.cap < e.index_sketch.org.cap) e.raw_sketch.org.swap(e.index_sketch.org);
+    if (e.sketch.raw_sketch.val.cap < e.sketch.index_sketch.val.cap) e.sketch.raw_sketch.val.swap(e.sketch.index_sketch.val);
+    if (e.sketch.raw_sketch.org.cap < e.sketch.index_sketch.org.cap) e.sketch.raw_sketch.org.swap(e.sketch.index_sketch.org);
   }
 }
 
@@ -127,37 +124,7 @@ long long* engine_option(EngineOptions& o, const char* name) {
 
 void engine_release_scratch(Engine& e) {
   if (e.stream) (void)rvn_stream_sync(e.stream);
-  e.query_ready = false;
-  DevBuf* bufs[] = {
-      &e.index.s_val[0], &e.index.s_val[1], &e.index.s_org[0], &e.index.s_org[1], &e.index.u_val, &e.index.u_start,
-      &e.index.table, &e.index.direct, &e.index_sketch.val, &e.index_sketch.org, &e.index_sketch.read_off, &e.query_sketch.val,
-      &e.query_sketch.org, &e.query_sketch.read_off, &e.raw_sketch.val, &e.raw_sketch.org, &e.raw_sketch.read_off,
-      &e.map_out.ovl, &e.map_out.ovl_read_off, &e.map_out.filtered, &e.map_out.anchors, &e.map_out.anchor_off,
-      &e.map_out.anchor_cnt, &e.tmp_a, &e.tmp_b, &e.tmp_c, &e.tmp_d, &e.tmp_e, &e.tmp_f, &e.scan_tmp, &e.sort_tmp,
-      &e.q_start, &e.q_cnt, &e.m_off, &e.m_grp[0], &e.m_grp[1], &e.m_pos[0], &e.m_pos[1], &e.seg_off, &e.iv_slot_begin,
-      &e.iv_slot_end, &e.iv_cnt, &e.iv_off, &e.iv_begin, &e.iv_end, &e.lis_min, &e.lis_pred, &e.lis_tail, &e.lis_mask,
-      &e.ovl_slots, &e.ovl_flags, &e.ovl_scan, &e.chain_big, &e.sh_hist, &e.sh_off, &e.sh_ptrs, &e.poa_scratch, &e.poa2_scratch, &e.polish_quals, &e.ed_cnt, &e.ed_sort, &e.ed_todo, &e.p2_slot,
-      &e.p2_pairs, &e.p2_dist, &e.p2_regions, &e.p2_index_of, &e.p2_kmers_off, &e.p2_ok, &e.p2_keep, &e.p2_tmp_ovl,
-      &e.poa_sched, &e.poa_redo_w, &e.poa_redo_i, &e.nw_hs, &e.nw_ck, &e.nw_hs2, &e.nw_ck2, &e.nw_hs3, &e.nw_ck3, &e.nw_hs4, &e.nw_ck4, &e.nw_strip, &e.nw_jobs, &e.nw_res,
-      &e.pl_best, &e.pl_best_t, &e.pl_idmap, &e.pl_recs, &e.pl_keep, &e.pl_win_cnt, &e.pl_win_off, &e.pl_win_fill,
-      &e.pl_win_meta, &e.pl_first_window, &e.pl_keys, &e.pl_lays_tmp, &e.pl_lays, &e.pl_wins, &e.pl_out, &e.pl_len,
-      &e.pl_status, &e.pl_ok, &e.pl_cons_off, &e.pl_final, &e.pl_qual_off, &e.pl_misc, &e.anc_slot_off, &e.anc_slot_cnt};
-  for (DevBuf* b : bufs) b->release();
-  e.pl_last_valid = false;
-  e.polish_sketches.clear();  // (the reads' sketch kept between polishing rounds: derived data, recomputed when needed)
-  e.polish_sketch_owner = 0;
-  e.pl_tval.release();
-  e.pl_torg.release();
-  e.foreign_val.release();
-  e.foreign_org.release();
-  e.index.m = e.index.u = 0;
-  e.index.table_built = false;
-  e.index.direct_built = false;
-  e.map_out.n_query = e.map_out.n_matches = e.map_out.n_intervals = e.map_out.n_overlaps = 0;
-  e.map_out.first = e.map_out.last = 0;
-  e.map_out.has_anchors = false;
-  e.polish_last_windows = 0;
-  e.polish_last_layers = 0;
+  e.for_each_group([](auto& group) { group.release(); });
   delete e.pile_pool;
   e.pile_pool = nullptr;
 }
@@ -250,14 +217,6 @@ void rvn_engine_destroy(rvn_engine* h) {
   if (h->e.stream) (void)rvn_stream_sync(h->e.stream);
   if (h->e.ev0) (void)hipEventDestroy(h->e.ev0);
   if (h->e.ev1) (void)hipEventDestroy(h->e.ev1);
-  for (hipEvent_t ev : h->e.nw_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (hipStream_t st2 : h->e.nw_streams)
-    if (st2) (void)hipStreamDestroy(st2);
-  for (hipEvent_t ev : h->e.nw_side_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (hipStream_t st2 : h->e.nw_side)
-    if (st2) (void)hipStreamDestroy(st2);
   if (h->e.stream) (void)hipStreamDestroy(h->e.stream);
   if (h->e.h_pin) (void)hipHostFree(h->e.h_pin);
   delete h->e.pile_pool;
@@ -328,14 +287,14 @@ void rvn_engine_reset_stats(rvn_engine* h) {
   e.ktimers.reset();
   e.c_index_bases = e.c_index_min = e.c_index_keys = e.c_query_bases = e.c_query_min = e.c_matches = e.c_overlaps =
       e.c_intervals = 0;
-  e.poa_cells_full = e.poa_cells_band = e.poa_calls = 0;
+  e.poa.cells_full = e.poa.cells_band = e.poa.calls = 0;
 }
 
 void rvn_poa_work(const rvn_engine* h, uint64_t out[3]) {
   if (!h || !out) return;
-  out[0] = h->e.poa_cells_full;
-  out[1] = h->e.poa_cells_band;
-  out[2] = h->e.poa_calls;
+  out[0] = h->e.poa.cells_full;
+  out[1] = h->e.poa.cells_band;
+  out[2] = h->e.poa.calls;
 }
 
 void rvn_engine_set_timing(rvn_engine* h, int enabled) {

@@ -152,14 +152,14 @@ __global__ __launch_bounds__(256) void occ_quantile_kernel(const u32* __restrict
 template <typename V>
 void index_runs_impl(Engine& e) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   const u64 m = ix.m;
   StageTimer t(e, StageTimes::kIndex);
   const V* sv = ix.s_val[ix.cur].as<V>();
-  u8* flags = e.tmp_c.get<u8>(m + 1);
-  u32* fscan = e.tmp_d.get<u32>(m + 1);
+  u8* flags = e.scratch.tmp_c.get<u8>(m + 1);
+  u32* fscan = e.scratch.tmp_d.get<u32>(m + 1);
   RVN_KLAUNCH(kKHeads, heads_kernel<V><<<div_up(m, 256), 256, 0, s>>>(sv, m, flags));
-  exclusive_scan_u8_u32(flags, fscan, m, e.scan_tmp, s);
+  exclusive_scan_u8_u32(flags, fscan, m, e.scratch.scan_tmp, s);
   const u32 u = static_cast<u32>(read_back(e, fscan + m, 4));
   ix.u = u;
   V* u_val = ix.u_val.get<V>(static_cast<size_t>(u) + 1);
@@ -173,7 +173,7 @@ constexpr u32 kDirectMinKeys = 8u << 20;  // distinct values from which the dire
 template <typename V>
 void index_table_impl(Engine& e) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   if (ix.table_built || ix.m == 0) return;
   StageTimer t(e, StageTimes::kIndex);
   const u32 u = static_cast<u32>(ix.u);
@@ -216,7 +216,7 @@ void index_table_impl(Engine& e) {
 template <typename V>
 void index_build_impl(Engine& e, Sketch& sk, bool build_table) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   const u64 m = sk.count;
   ix.m = m;
   ix.u = 0;
@@ -247,10 +247,10 @@ void index_build_impl(Engine& e, Sketch& sk, bool build_table) {
     StageTimer t(e, StageTimes::kSort);
     if (sizeof(V) == 4)
       ix.cur = radix_sort_pairs_u32_u64(reinterpret_cast<u32*>(v0), reinterpret_cast<u32*>(v1), o0, o1, m, 2 * e.k,
-                                        e.sort_tmp, e.scan_tmp, s, kKRsUpsweep, kKRsDownsweep, false);
+                                        e.scratch.sort_tmp, e.scratch.scan_tmp, s, kKRsUpsweep, kKRsDownsweep, false);
     else
       ix.cur = radix_sort_pairs_u64_u64(reinterpret_cast<u64*>(v0), reinterpret_cast<u64*>(v1), o0, o1, m, 2 * e.k,
-                                        e.sort_tmp, e.scan_tmp, s, kKRsUpsweep, kKRsDownsweep, false);
+                                        e.scratch.sort_tmp, e.scratch.scan_tmp, s, kKRsUpsweep, kKRsDownsweep, false);
     t.stop();
   }
   ix.table_built = false;
@@ -262,8 +262,8 @@ void index_build_impl(Engine& e, Sketch& sk, bool build_table) {
 }  // namespace
 
 void index_build(Engine& e, Sketch& sk, bool build_table) {
-  e.index.first = sk.first;
-  e.index.last = sk.last;
+  e.sketch.index.first = sk.first;
+  e.sketch.index.last = sk.last;
   if (e.val64) index_build_impl<u64>(e, sk, build_table);
   else index_build_impl<u32>(e, sk, build_table);
 }
@@ -276,14 +276,14 @@ void index_build_table(Engine& e) {
 // Count-of-counts histogram of the per-key run lengths (bins 0..65534; `over` = the run lengths >= 65535): what a
 // rank contributes to the all-reduce behind the sharded pass's global Filter.
 void index_key_histogram(Engine& e, std::vector<u64>& hist, std::vector<u32>& over) {
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   hist.assign(kHistBins, 0);
   over.clear();
   if (ix.u == 0) return;
   hipStream_t s = e.stream;
   const u32 overflow_cap = 1u << 20;
-  u32* d_hist = e.tmp_a.get<u32>(kHistBins + 1);
-  u32* d_over = e.tmp_b.get<u32>(overflow_cap + 1);
+  u32* d_hist = e.scratch.tmp_a.get<u32>(kHistBins + 1);
+  u32* d_over = e.scratch.tmp_b.get<u32>(overflow_cap + 1);
   RVN_HIP(hipMemsetAsync(d_hist, 0, (kHistBins + 1) * 4, s));
   const u32 u = static_cast<u32>(ix.u);
   const u32 grid = std::min<u32>(div_up(u, 256), 2048);
@@ -302,7 +302,7 @@ void index_key_histogram(Engine& e, std::vector<u64>& hist, std::vector<u32>& ov
 
 // ram Filter: occurrence_ = (value at index (1-f)*U of the sorted per-key counts) + 1; f == 0 -> no filter.
 void index_filter(Engine& e, double freq) {
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   if (freq == 0 || ix.u == 0) {
     ix.occurrence = 0xFFFFFFFFu;
     return;
@@ -310,15 +310,15 @@ void index_filter(Engine& e, double freq) {
   StageTimer t(e, StageTimes::kFilter);
   hipStream_t s = e.stream;
   const u32 overflow_cap = 1u << 20;
-  u32* hist = e.tmp_a.get<u32>(kHistBins + 1);
-  u32* ovl = e.tmp_b.get<u32>(overflow_cap + 1);
+  u32* hist = e.scratch.tmp_a.get<u32>(kHistBins + 1);
+  u32* ovl = e.scratch.tmp_b.get<u32>(overflow_cap + 1);
   RVN_HIP(hipMemsetAsync(hist, 0, (kHistBins + 1) * 4, s));
   const u32 u = static_cast<u32>(ix.u);
   const u32 grid = std::min<u32>(div_up(u, 256), 2048);
   RVN_KLAUNCH(kKOccHist, occ_hist_kernel<<<grid, 256, 0, s>>>(ix.u_start.as<u32>(), u, hist, ovl, hist + kHistBins, overflow_cap, nullptr));
   size_t nth = static_cast<size_t>((1 - freq) * u);
   if (nth >= u) nth = u - 1;
-  u64* qout = e.tmp_e.get<u64>(4);
+  u64* qout = e.scratch.tmp_e.get<u64>(4);
   RVN_KLAUNCH(kKOccHist, occ_quantile_kernel<<<1, 256, 0, s>>>(hist, nth, qout));
   RVN_HIP(hipMemcpyAsync(e.h_pin, qout, 16, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(e.h_pin + 2, hist + kHistBins, 4, hipMemcpyDeviceToHost, s));

@@ -115,16 +115,16 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
   opt.debug = knob("RVN_IO_DEBUG") != nullptr;
   // the slabs are page-locked once per engine and handed out again by later loads (pinning runs at 1-2 GB/s)
   opt.alloc = [&e](size_t n) -> void* {
-    for (auto& slot : e.io_pin)
+    for (auto& slot : e.io.pin)
       if (!slot.second && slot.first->cap >= n) {
         slot.second = true;
         return slot.first->ptr;
       }
-    e.io_pin.emplace_back(std::unique_ptr<PinBuf>(new PinBuf()), true);
-    return e.io_pin.back().first->get<u8>(n);
+    e.io.pin.emplace_back(std::unique_ptr<PinBuf>(new PinBuf()), true);
+    return e.io.pin.back().first->get<u8>(n);
   };
   opt.release = [&e](void* p) {
-    for (auto& slot : e.io_pin)
+    for (auto& slot : e.io.pin)
       if (slot.first->ptr == p) slot.second = false;
   };
   speculated = false;
@@ -141,7 +141,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
   std::vector<u64> h_qoff(1, 0);
   u64 words_used = 0, qblocks_used = 0;
   DevBuf d_foff, d_qfoff, d_len, d_woff, d_qoff;
-  u32* d_bad = e.tmp_f.get<u32>(4);
+  u32* d_bad = e.scratch.tmp_f.get<u32>(4);
   RVN_HIP(hipMemsetAsync(d_bad, 0, 4, s));
 
   // the kept text in HBM: d_text[cur][0] is offset text_base of the kept text
@@ -172,7 +172,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
         qoff[i + 1] = qoff[i] + (recs[i].len + 63) / 64;
       }
       const u64 nw = woff[nr], nq = qoff[nr];
-      const u8* text = e.io_text[cur].as<u8>();
+      const u8* text = e.io.text[cur].as<u8>();
       u64* dfo = d_foff.get<u64>(nr);
       u32* dln = d_len.get<u32>(nr);
       u64* dwo = d_woff.get<u64>(nr + 1);
@@ -210,9 +210,9 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
     if (!last) {  // the record in progress moves to the front of the other text buffer
       const u64 from = std::max(text_base, std::min(scanner.retain_from(), text_end));
       const u64 tail = text_end - from;
-      e.io_text[cur ^ 1].reserve(std::max<u64>(tail + (64ULL << 20), kShipBytes + (64ULL << 20)));
+      e.io.text[cur ^ 1].reserve(std::max<u64>(tail + (64ULL << 20), kShipBytes + (64ULL << 20)));
       if (tail)
-        RVN_HIP(hipMemcpyAsync(e.io_text[cur ^ 1].ptr, e.io_text[cur].as<u8>() + (from - text_base), tail,
+        RVN_HIP(hipMemcpyAsync(e.io.text[cur ^ 1].ptr, e.io.text[cur].as<u8>() + (from - text_base), tail,
                                hipMemcpyDeviceToDevice, s));
       text_base = from;
       cur ^= 1;
@@ -232,7 +232,7 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
       (void)hipEventDestroy(ev[1]);
     }
   } guard{ev, s};
-  e.io_text[0].reserve(kShipBytes + (64ULL << 20));
+  e.io.text[0].reserve(kShipBytes + (64ULL << 20));
 
   u8* slab = nullptr;
   u64 n = 0, k = 0;
@@ -244,9 +244,9 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
     scan_busy += secs(t0);
     const auto t1 = std::chrono::steady_clock::now();
     if (run_base < text_base) throw std::logic_error("[raven_hip] input path: run before the retained text");
-    e.io_text[cur].grow_keeping(run_base - text_base, run_base - text_base + run_len + 64, s);
+    e.io.text[cur].grow_keeping(run_base - text_base, run_base - text_base + run_len + 64, s);
     if (run_len)
-      RVN_HIP(hipMemcpyAsync(e.io_text[cur].as<u8>() + (run_base - text_base), run, run_len, hipMemcpyHostToDevice, s));
+      RVN_HIP(hipMemcpyAsync(e.io.text[cur].as<u8>() + (run_base - text_base), run, run_len, hipMemcpyHostToDevice, s));
     RVN_HIP(hipEventRecord(ev[k & 1], s));
     if (k > 0) {  // slab k-1 has been copied: the pool may overwrite it (slab k is still in flight)
       RVN_HIP(hipEventSynchronize(ev[(k - 1) & 1]));
@@ -260,8 +260,8 @@ void load_once(Engine& e, const std::string& path, bool fastq, bool streaming, b
     u8 extra = 0;
     const u64 at = scanner.text_end();
     if (scanner.finish(recs, rec_names, &extra)) {
-      e.io_text[cur].grow_keeping(at - text_base, at - text_base + 64, s);
-      RVN_HIP(hipMemcpy(e.io_text[cur].as<u8>() + (at - text_base), &extra, 1, hipMemcpyHostToDevice));
+      e.io.text[cur].grow_keeping(at - text_base, at - text_base + 64, s);
+      RVN_HIP(hipMemcpy(e.io.text[cur].as<u8>() + (at - text_base), &extra, 1, hipMemcpyHostToDevice));
     }
     const auto t1 = std::chrono::steady_clock::now();
     ship(true);

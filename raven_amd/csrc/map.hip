@@ -1085,25 +1085,25 @@ __global__ void read_ovl_off_kernel(const u64* __restrict__ seg_off, const u32* 
 
 }  // namespace
 
-// Chain stage: matches of reads [first, last) are in e.m_grp[0] / e.m_pos[0] (both ping-pong sides reserved for
-// H + 1 entries), segmented per read by e.seg_off[nr + 1] -> overlaps in (read, emission) order in `out`.
+// Chain stage: matches of reads [first, last) are in e.map.m_grp[0] / e.map.m_pos[0] (both ping-pong sides reserved for
+// H + 1 entries), segmented per read by e.map.seg_off[nr + 1] -> overlaps in (read, emission) order in `out`.
 // (ram Map after the index probes: sort by group, diagonal bands, per-band LIS, overlap emission.)
 void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, MapOut& out) {
   hipStream_t s = e.stream;
   const u32 nr = last - first;
   u32* ovl_read_off = out.ovl_read_off.get<u32>(static_cast<size_t>(nr) + 1);
-  u64* seg_off = e.seg_off.as<u64>();
+  u64* seg_off = e.map.seg_off.as<u64>();
   if (H == 0) {
     RVN_HIP(hipMemsetAsync(ovl_read_off, 0, (static_cast<size_t>(nr) + 1) * 4, s));
     return;
   }
-  u64* g0 = e.m_grp[0].as<u64>();
-  u64* g1 = e.m_grp[1].as<u64>();
-  u64* p0 = e.m_pos[0].as<u64>();
-  u64* p1 = e.m_pos[1].as<u64>();
+  u64* g0 = e.map.m_grp[0].as<u64>();
+  u64* g1 = e.map.m_grp[1].as<u64>();
+  u64* p0 = e.map.m_pos[0].as<u64>();
+  u64* p1 = e.map.m_pos[1].as<u64>();
   {
     StageTimer t(e, StageTimes::kSegSort);
-    u32* lists = e.chain_big.get<u32>(static_cast<size_t>(nr) * (kSegClasses + 1) + 16);
+    u32* lists = e.map.chain_big.get<u32>(static_cast<size_t>(nr) * (kSegClasses + 1) + 16);
     u32* d_cnt = lists + static_cast<size_t>(nr) * (kSegClasses + 1);
     RVN_HIP(hipMemsetAsync(d_cnt, 0, (kSegClasses + 1) * 4, s));
     seg_class_list_kernel<<<div_up(nr, 256), 256, 0, s>>>(seg_off, nr, lists, d_cnt);
@@ -1139,18 +1139,18 @@ void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, Map
   const u64 n_slots4 = (H + 3) / 4 + 1;
   {
     StageTimer t(e, StageTimes::kIntervals);
-    u64* slot_begin = e.iv_slot_begin.get<u64>(n_slots4 + 1);
-    u64* slot_end = e.iv_slot_end.get<u64>(n_slots4 + 1);
-    u32* iv_cnt = e.iv_cnt.get<u32>(static_cast<size_t>(nr) + 1);
-    u32* iv_off = e.iv_off.get<u32>(static_cast<size_t>(nr) + 2);
+    u64* slot_begin = e.map.iv_slot_begin.get<u64>(n_slots4 + 1);
+    u64* slot_end = e.map.iv_slot_end.get<u64>(n_slots4 + 1);
+    u32* iv_cnt = e.map.iv_cnt.get<u32>(static_cast<size_t>(nr) + 1);
+    u32* iv_off = e.map.iv_off.get<u32>(static_cast<size_t>(nr) + 2);
     RVN_KLAUNCH(kKIntervals, intervals_kernel<<<div_up(nr, 4), 256, 0, s>>>(g0, seg_off, nr, e.bandwidth, slot_begin, slot_end, iv_cnt));
-    exclusive_scan_u32_u32(iv_cnt, iv_off, nr, e.scan_tmp, s);
+    exclusive_scan_u32_u32(iv_cnt, iv_off, nr, e.scratch.scan_tmp, s);
     NI = static_cast<u32>(read_back(e, iv_off + nr, 4));
     out.n_intervals = NI;
     if (NI) {
-      u64* iv_begin = e.iv_begin.get<u64>(static_cast<size_t>(NI) + 1);
-      u64* iv_end = e.iv_end.get<u64>(static_cast<size_t>(NI) + 1);
-      u32* iv_read = e.tmp_b.get<u32>(static_cast<size_t>(NI) + 1);
+      u64* iv_begin = e.map.iv_begin.get<u64>(static_cast<size_t>(NI) + 1);
+      u64* iv_end = e.map.iv_end.get<u64>(static_cast<size_t>(NI) + 1);
+      u32* iv_read = e.scratch.tmp_b.get<u32>(static_cast<size_t>(NI) + 1);
       RVN_KLAUNCH(kKIntervalsGather, intervals_gather_kernel<<<div_up(nr, 4), 256, 0, s>>>(
                                          slot_begin, slot_end, seg_off, iv_off, nr, iv_begin, iv_end, iv_read));
     }
@@ -1162,15 +1162,15 @@ void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, Map
   }
   const u32 slot_div = std::max(1u, std::min(4u, e.chain));
   const u64 n_slots = (H + slot_div - 1) / slot_div + 1;
-  Overlap* slots = e.ovl_slots.get<Overlap>(n_slots + 1);
-  u8* slot_flags = e.ovl_flags.get<u8>(n_slots + 1);
+  Overlap* slots = e.map.ovl_slots.get<Overlap>(n_slots + 1);
+  u8* slot_flags = e.map.ovl_flags.get<u8>(n_slots + 1);
   {
     StageTimer t(e, StageTimes::kChain);
-    u64* iv_begin = e.iv_begin.as<u64>();
-    u64* iv_end = e.iv_end.as<u64>();
-    u32* iv_read = e.tmp_b.as<u32>();
+    u64* iv_begin = e.map.iv_begin.as<u64>();
+    u64* iv_end = e.map.iv_end.as<u64>();
+    u32* iv_read = e.scratch.tmp_b.as<u32>();
     // size classes of the intervals (position sort and chain kernels both go by them)
-    u32* lists = e.chain_big.get<u32>(static_cast<size_t>(NI) * (kChainClasses + 1) + 16);
+    u32* lists = e.map.chain_big.get<u32>(static_cast<size_t>(NI) * (kChainClasses + 1) + 16);
     u32* d_cnt = lists + static_cast<size_t>(NI) * (kChainClasses + 1);
     RVN_HIP(hipMemsetAsync(d_cnt, 0, (kChainClasses + 1) * 4, s));
     chain_class_list_kernel<<<div_up(NI, 256), 256, 0, s>>>(iv_begin, iv_end, NI, e.chain, lists, d_cnt);
@@ -1202,18 +1202,18 @@ void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, Map
         RVN_KLAUNCH(kKSegSortPos, seg_sort_pos_lds_kernel<256><<<n_cls[c], 256, seg_sort_lds_bytes<256, false>(cap), s>>>(
                                       p0, iv_begin, iv_end, list, n_cls[c], cap));
     }
-    u32* lis_min = e.lis_min.get<u32>(H + NI + 1);
-    u32* lis_pred = e.lis_pred.get<u32>(H + 1);
-    u64* lis_tail = e.lis_tail.get<u64>(H + NI + 1);
-    u64* lis_mask = e.lis_mask.get<u64>((H >> 6) + NI + 2);
+    u32* lis_min = e.map.lis_min.get<u32>(H + NI + 1);
+    u32* lis_pred = e.map.lis_pred.get<u32>(H + 1);
+    u64* lis_tail = e.map.lis_tail.get<u64>(H + NI + 1);
+    u64* lis_mask = e.map.lis_mask.get<u64>((H >> 6) + NI + 2);
     RVN_HIP(hipMemsetAsync(slot_flags, 0, n_slots + 1, s));
     u64* anchors = nullptr;
     u64* slot_aoff = nullptr;
     u32* slot_acnt = nullptr;
-    if (e.keep_anchors) {
+    if (e.map.keep_anchors) {
       anchors = out.anchors.get<u64>(H + 1);
-      slot_aoff = e.anc_slot_off.get<u64>(n_slots + 1);
-      slot_acnt = e.anc_slot_cnt.get<u32>(n_slots + 1);
+      slot_aoff = e.map.anc_slot_off.get<u64>(n_slots + 1);
+      slot_acnt = e.map.anc_slot_cnt.get<u32>(n_slots + 1);
     }
     RVN_KLAUNCH(kKChainSmall, chain_small_kernel<<<div_up(NI, 64), 64, 0, s>>>(
                                   g0, p0, iv_begin, iv_end, iv_read, NI, r.id.as<u32>(), first, e.k, e.chain, e.matches,
@@ -1235,19 +1235,19 @@ void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, Map
   }
   {
     StageTimer t(e, StageTimes::kCompact);
-    u32* scan = e.ovl_scan.get<u32>(n_slots + 2);
-    exclusive_scan_u8_u32(slot_flags, scan, n_slots, e.scan_tmp, s);
+    u32* scan = e.map.ovl_scan.get<u32>(n_slots + 2);
+    exclusive_scan_u8_u32(slot_flags, scan, n_slots, e.scratch.scan_tmp, s);
     const u32 O = static_cast<u32>(read_back(e, scan + n_slots, 4));
     out.n_overlaps = O;
     e.c_overlaps += O;
     Overlap* ovl = out.ovl.get<Overlap>(static_cast<size_t>(O) + 1);
     RVN_KLAUNCH(kKCompactOverlaps, compact_overlaps_kernel<<<div_up(n_slots, 256), 256, 0, s>>>(slots, slot_flags, scan, n_slots, ovl));
-    out.has_anchors = e.keep_anchors;
-    if (e.keep_anchors) {
+    out.has_anchors = e.map.keep_anchors;
+    if (e.map.keep_anchors) {
       u64* aoff = out.anchor_off.get<u64>(static_cast<size_t>(O) + 1);
       u32* acnt = out.anchor_cnt.get<u32>(static_cast<size_t>(O) + 1);
       RVN_KLAUNCH(kKCompactOverlaps, compact_aux_kernel<<<div_up(n_slots, 256), 256, 0, s>>>(
-                                         e.anc_slot_off.as<u64>(), e.anc_slot_cnt.as<u32>(), slot_flags, scan, n_slots,
+                                         e.map.anc_slot_off.as<u64>(), e.map.anc_slot_cnt.as<u32>(), slot_flags, scan, n_slots,
                                          aoff, acnt));
     }
     RVN_KLAUNCH(kKGather, read_ovl_off_kernel<<<div_up(nr + 1, 256), 256, 0, s>>>(seg_off, scan, slot_div, nr + 1, ovl_read_off));
@@ -1259,35 +1259,35 @@ namespace {
 
 // The probe branch of Map's match stage: every minimizer of the query sketch qs (nq = qs.count > 0 minimizers of nr reads,
 // qs.read_off their per-read offsets) looked up in the engine's index (m > 0; its table is built here if it is not yet).
-// The matches land in e.m_grp[0] / e.m_pos[0] in (query minimizer, run) order, their per-read offsets in seg_off[nr + 1]
+// The matches land in e.map.m_grp[0] / e.map.m_pos[0] in (query minimizer, run) order, their per-read offsets in seg_off[nr + 1]
 // (not written when there is no match); filt (nullable): per-minimizer "skipped by the occurrence filter".  Returns the
 // number of matches.  Called by map_batch_impl and by the test hook rvn_test_match_probe below.
 template <typename V>
 u64 match_probe(Engine& e, const Sketch& qs, u32 nr, bool avoid_equal, bool avoid_symmetric, u8* filt, u64* seg_off) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   index_build_table(e);
   const u64 nq = qs.count;
   StageTimer t(e, StageTimes::kMatch);
-  u32* q_start = e.q_start.get<u32>(nq + 1);
-  u32* q_n = e.tmp_a.get<u32>(nq + 1);
-  u32* q_cnt = e.q_cnt.get<u32>(nq + 1);
-  u64* m_off = e.m_off.get<u64>(nq + 2);
+  u32* q_start = e.map.q_start.get<u32>(nq + 1);
+  u32* q_n = e.scratch.tmp_a.get<u32>(nq + 1);
+  u32* q_cnt = e.map.q_cnt.get<u32>(nq + 1);
+  u64* m_off = e.map.m_off.get<u64>(nq + 2);
   RVN_KLAUNCH(kKMatchCount, match_count_kernel<V><<<div_up(nq, 256), 256, 0, s>>>(
       qs.val.as<V>(), qs.org.as<u64>(), nq, ix.u_val.as<V>(), ix.u_start.as<u32>(), ix.table.as<u32>(), ix.shift,
       static_cast<u32>(ix.u), ix.s_org[ix.cur].as<u64>(), ix.occurrence, avoid_equal, avoid_symmetric, q_start, q_n,
       q_cnt, filt, ix.direct_built ? ix.direct.as<u64>() : nullptr));
-  exclusive_scan_u32_u64(q_cnt, m_off, nq, e.scan_tmp, s);
+  exclusive_scan_u32_u64(q_cnt, m_off, nq, e.scratch.scan_tmp, s);
   const u64 H = read_back(e, m_off + nq, 8);
   if (H) {
-    u64* g0 = e.m_grp[0].get<u64>(H + 1);
-    u64* p0 = e.m_pos[0].get<u64>(H + 1);
-    e.m_grp[1].reserve((H + 1) * 8);
-    e.m_pos[1].reserve((H + 1) * 8);
+    u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
+    u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
+    e.map.m_grp[1].reserve((H + 1) * 8);
+    e.map.m_pos[1].reserve((H + 1) * 8);
     RVN_KLAUNCH(kKMatchEmit, match_emit_kernel<<<div_up(nq, 256), 256, 0, s>>>(qs.org.as<u64>(), nq, ix.s_org[ix.cur].as<u64>(), q_start,
                                                       q_n, m_off, avoid_equal, avoid_symmetric, g0, p0));
     RVN_KLAUNCH(kKGather, gather_u64_by_u32_kernel<<<div_up(nr + 1, 256), 256, 0, s>>>(
-                              e.m_off.as<u64>(), qs.read_off.as<u32>(), seg_off, nr + 1));
+                              e.map.m_off.as<u64>(), qs.read_off.as<u32>(), seg_off, nr + 1));
   }
   t.stop();
   return H;
@@ -1297,25 +1297,25 @@ template <typename V>
 void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoid_equal, bool avoid_symmetric,
                     bool minhash, bool want_filtered, MapOut& out) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   const u32 nr = last - first;
   out.first = first;
   out.last = last;
   out.n_query = out.n_matches = out.n_intervals = out.n_overlaps = 0;
   u32* ovl_read_off = out.ovl_read_off.get<u32>(static_cast<size_t>(nr) + 1);
 
-  u64* seg_off = e.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+  u64* seg_off = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
   u64 H = 0;
   // self-join path: queries == indexed reads, flags in the index, bounded run lengths, ids == read indices
   const bool join = minhash && !want_filtered && ix.m != 0 && ix.first == first && ix.last == last &&
                     (ix.has_query_flags || ix.all_query) && ix.occurrence <= 4096 && r.ids_are_indices;
   if (join) {
     StageTimer t(e, StageTimes::kMatch);
-    e.query_ready = false;
+    e.sketch.query_ready = {};
     for (u32 i = first; i < last; ++i) e.c_query_bases += r.h_len[i];
-    out.n_query = ix.all_query ? ix.m : e.join_query_count;
+    out.n_query = ix.all_query ? ix.m : e.sketch.join_query_count;
     e.c_query_min += out.n_query;
-    u32* read_cnt = e.q_cnt.get<u32>(2 * (static_cast<size_t>(nr) + 1));
+    u32* read_cnt = e.map.q_cnt.get<u32>(2 * (static_cast<size_t>(nr) + 1));
     u32* cursor = read_cnt + nr + 1;
     RVN_HIP(hipMemsetAsync(read_cnt, 0, 2 * (static_cast<size_t>(nr) + 1) * 4, s));
     const u32 n_runs = static_cast<u32>(ix.u);
@@ -1324,28 +1324,28 @@ void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoi
                                  ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, ix.all_query, avoid_equal,
                                  avoid_symmetric, r.h_id.empty() ? 0 : r.h_id[first], 0u, 0xFFFFFFFFu, read_cnt, nullptr, nullptr,
                                  nullptr, nullptr));
-    exclusive_scan_u32_u64(read_cnt, seg_off, nr, e.scan_tmp, s);
+    exclusive_scan_u32_u64(read_cnt, seg_off, nr, e.scratch.scan_tmp, s);
     H = read_back(e, seg_off + nr, 8);
     out.n_matches = H;
     e.c_matches += H;
     if (H) {
-      u64* g0 = e.m_grp[0].get<u64>(H + 1);
-      u64* p0 = e.m_pos[0].get<u64>(H + 1);
-      e.m_grp[1].reserve((H + 1) * 8);
-      e.m_pos[1].reserve((H + 1) * 8);
+      u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
+      u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
+      e.map.m_grp[1].reserve((H + 1) * 8);
+      e.map.m_pos[1].reserve((H + 1) * 8);
       RVN_KLAUNCH(kKJoinEmit, join_kernel<true><<<div_up(n_runs, 256), 256, 0, s>>>(
                                   ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, ix.all_query, avoid_equal,
                                   avoid_symmetric, r.h_id[first], 0u, 0xFFFFFFFFu, nullptr, seg_off, cursor, g0, p0));
     }
     t.stop();
   }
-  Sketch& qs = e.query_sketch;
+  Sketch& qs = e.sketch.query_sketch;
   if (!join) {
   {
     StageTimer t(e, StageTimes::kQuery);
-    const bool ready = e.query_ready && e.query_ready_first == first && e.query_ready_last == last &&
-                       e.query_ready_minhash == minhash;
-    e.query_ready = false;
+    const SketchState::QueryReady& q = e.sketch.query_ready;
+    const bool ready = q.valid && q.first == first && q.last == last && q.minhash == minhash;
+    e.sketch.query_ready = {};
     if (!ready) sketch_range(e, r, first, last, minhash, qs);
     t.stop();
   }
@@ -1371,18 +1371,18 @@ void map_batch_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoi
 }  // namespace
 
 // Self-join of the whole (shard of the) index for query read ids 0..n_reads-1 (ids are global read indices):
-// matches land in e.m_grp[0] / e.m_pos[0], segmented by query id through e.seg_off[n_reads + 1].  The hash-owner
+// matches land in e.map.m_grp[0] / e.map.m_pos[0], segmented by query id through e.map.seg_off[n_reads + 1].  The hash-owner
 // side of the sharded pass: the owner of a hash class joins its runs and ships every read's matches
 // to the GPU that owns the read.  Returns the number of matches.
 u64 join_index_matches(Engine& e, u32 n_reads, bool avoid_equal, bool avoid_symmetric, u32 q_lo, u32 q_hi) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
-  u64* seg_off = e.seg_off.get<u64>(static_cast<size_t>(n_reads) + 2);
+  Index& ix = e.sketch.index;
+  u64* seg_off = e.map.seg_off.get<u64>(static_cast<size_t>(n_reads) + 2);
   RVN_HIP(hipMemsetAsync(seg_off, 0, (static_cast<size_t>(n_reads) + 2) * 8, s));
   if (ix.m == 0 || ix.u == 0) return 0;
   if (!(ix.has_query_flags || ix.all_query)) throw std::invalid_argument("[raven_hip] join: index has no query flags");
   StageTimer t(e, StageTimes::kMatch);
-  u32* read_cnt = e.q_cnt.get<u32>(2 * (static_cast<size_t>(n_reads) + 1));
+  u32* read_cnt = e.map.q_cnt.get<u32>(2 * (static_cast<size_t>(n_reads) + 1));
   u32* cursor = read_cnt + n_reads + 1;
   RVN_HIP(hipMemsetAsync(read_cnt, 0, 2 * (static_cast<size_t>(n_reads) + 1) * 4, s));
   const u32 n_runs = static_cast<u32>(ix.u);
@@ -1390,11 +1390,11 @@ u64 join_index_matches(Engine& e, u32 n_reads, bool avoid_equal, bool avoid_symm
   RVN_KLAUNCH(kKJoinCount, join_kernel<false><<<div_up(n_runs, 256), 256, 0, s>>>(
                                ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, ix.all_query, avoid_equal,
                                avoid_symmetric, 0, q_lo, q_hi, read_cnt, nullptr, nullptr, nullptr, nullptr));
-  exclusive_scan_u32_u64(read_cnt, seg_off, n_reads, e.scan_tmp, s);
+  exclusive_scan_u32_u64(read_cnt, seg_off, n_reads, e.scratch.scan_tmp, s);
   const u64 H = read_back(e, seg_off + n_reads, 8);
   e.c_matches += H;
-  u64* g0 = e.m_grp[0].get<u64>(H + 1);
-  u64* p0 = e.m_pos[0].get<u64>(H + 1);
+  u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
+  u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
   if (H)
     RVN_KLAUNCH(kKJoinEmit, join_kernel<true><<<div_up(n_runs, 256), 256, 0, s>>>(
                                 ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, ix.all_query, avoid_equal,
@@ -1409,21 +1409,21 @@ u64 join_index_matches(Engine& e, u32 n_reads, bool avoid_equal, bool avoid_symm
 // (join_kernel above), extended to queries that are not members.  n_query: the query-only entries (statistics).
 void map_batch_query_only(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 n_query, MapOut& out) {
   hipStream_t s = e.stream;
-  Index& ix = e.index;
+  Index& ix = e.sketch.index;
   const u32 nr = last - first;
   out.first = first;
   out.last = last;
   out.n_query = n_query;
   out.n_matches = out.n_intervals = out.n_overlaps = 0;
   (void)out.ovl_read_off.get<u32>(static_cast<size_t>(nr) + 1);
-  u64* seg_off = e.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+  u64* seg_off = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
   u64 H = 0;
   {
     StageTimer t(e, StageTimes::kMatch);
-    e.query_ready = false;
+    e.sketch.query_ready = {};
     for (u32 i = first; i < last; ++i) e.c_query_bases += r.h_len[i];
     e.c_query_min += n_query;
-    u32* read_cnt = e.q_cnt.get<u32>(2 * (static_cast<size_t>(nr) + 1));
+    u32* read_cnt = e.map.q_cnt.get<u32>(2 * (static_cast<size_t>(nr) + 1));
     u32* cursor = read_cnt + nr + 1;
     RVN_HIP(hipMemsetAsync(read_cnt, 0, 2 * (static_cast<size_t>(nr) + 1) * 4, s));
     RVN_HIP(hipMemsetAsync(seg_off, 0, (static_cast<size_t>(nr) + 2) * 8, s));
@@ -1433,15 +1433,15 @@ void map_batch_query_only(Engine& e, const ReadsDev& r, u32 first, u32 last, u64
       RVN_KLAUNCH(kKJoinCount, join_kernel<false><<<div_up(n_runs, 256), 256, 0, s>>>(
                                    ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, 0, 0, 0, r.h_id[first], 0u, 0xFFFFFFFFu,
                                    read_cnt, nullptr, nullptr, nullptr, nullptr));
-      exclusive_scan_u32_u64(read_cnt, seg_off, nr, e.scan_tmp, s);
+      exclusive_scan_u32_u64(read_cnt, seg_off, nr, e.scratch.scan_tmp, s);
       H = read_back(e, seg_off + nr, 8);
     }
     e.c_matches += H;
     if (H) {
-      u64* g0 = e.m_grp[0].get<u64>(H + 1);
-      u64* p0 = e.m_pos[0].get<u64>(H + 1);
-      e.m_grp[1].reserve((H + 1) * 8);
-      e.m_pos[1].reserve((H + 1) * 8);
+      u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
+      u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
+      e.map.m_grp[1].reserve((H + 1) * 8);
+      e.map.m_pos[1].reserve((H + 1) * 8);
       RVN_KLAUNCH(kKJoinEmit, join_kernel<true><<<div_up(n_runs, 256), 256, 0, s>>>(
                                   ix.u_start.as<u32>(), n_runs, sorg, ix.occurrence, 0, 0, 0, r.h_id[first], 0u, 0xFFFFFFFFu,
                                   nullptr, seg_off, cursor, g0, p0));
@@ -1478,13 +1478,13 @@ static int test_match_probe(Engine& e, const u64* q_values, const u64* q_origins
     *p = static_cast<u64*>(std::malloc(8));
     if (!*p) throw std::bad_alloc();
   };
-  if (nq == 0 || e.index.m == 0) {  // (map_batch_impl returns before the match stage)
+  if (nq == 0 || e.sketch.index.m == 0) {  // (map_batch_impl returns before the match stage)
     empty(grp);
     empty(pos);
     return RVN_OK;
   }
-  Sketch& qs = e.query_sketch;
-  e.query_ready = false;
+  Sketch& qs = e.sketch.query_sketch;
+  e.sketch.query_ready = {};
   qs.first = 0;
   qs.last = nr;
   qs.count = nq;
@@ -1497,8 +1497,8 @@ static int test_match_probe(Engine& e, const u64* q_values, const u64* q_origins
   }
   RVN_HIP(hipMemcpy(qs.org.get<u64>(nq + 1), q_origins, nq * 8, hipMemcpyHostToDevice));
   RVN_HIP(hipMemcpy(qs.read_off.get<u32>(static_cast<size_t>(nr) + 1), q_read_off, (static_cast<size_t>(nr) + 1) * 4, hipMemcpyHostToDevice));
-  u8* d_filt = e.map_out.filtered.get<u8>(nq + 1);
-  u64* d_seg = e.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+  u8* d_filt = e.map.out.filtered.get<u8>(nq + 1);
+  u64* d_seg = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
   const u64 H = e.val64 ? match_probe<u64>(e, qs, nr, avoid_equal, avoid_symmetric, d_filt, d_seg)
                         : match_probe<u32>(e, qs, nr, avoid_equal, avoid_symmetric, d_filt, d_seg);
   RVN_HIP(hipMemcpy(filtered, d_filt, nq, hipMemcpyDeviceToHost));
@@ -1506,8 +1506,8 @@ static int test_match_probe(Engine& e, const u64* q_values, const u64* q_origins
   *pos = static_cast<u64*>(std::malloc((H + 1) * 8));
   if (!*grp || !*pos) throw std::bad_alloc();
   if (H) {
-    RVN_HIP(hipMemcpy(*grp, e.m_grp[0].ptr, H * 8, hipMemcpyDeviceToHost));
-    RVN_HIP(hipMemcpy(*pos, e.m_pos[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(*grp, e.map.m_grp[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(*pos, e.map.m_pos[0].ptr, H * 8, hipMemcpyDeviceToHost));
     RVN_HIP(hipMemcpy(seg_off, d_seg, (static_cast<size_t>(nr) + 1) * 8, hipMemcpyDeviceToHost));
   }
   *n_matches = H;

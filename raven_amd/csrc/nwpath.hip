@@ -312,6 +312,43 @@ u32 level_of(const NwJob& J) {
 // Fills the band fields of `jobs` (k, kcap, R, G, hs, ckpt) and produces every job's window records in d_recs
 // (records of a job start at its bp_off; jobs that cannot be aligned keep all-invalid records and are counted).
 //
+// The stage's streams and events, on first use.  HIP multiplexes its streams over a handful of hardware queues (four by
+// default): two walk streams that land on the same queue run one after the other, and the ~100-ms walk of the longest
+// alignments held the walk queued behind it — and with it the sweep waiting for that walk's buffer set
+// (profiles/r05_nw_timeline.csv: a walk starting the moment the long one ended).  Streams of another PRIORITY get hardware
+// queues of their own: the long pole's stream (set 3) is created at the highest priority, which also suits a kernel of 38
+// latency-bound waves.  ([4], the upload stream, must not share a hardware queue with the engine's stream either: its
+// copies run while a pass queued before is sweeping there.)  All or nothing: a creation that throws half-way must not
+// leave streams[0] set with the others null — the next call would skip this and launch walks on the null stream.
+void NwState::open() {
+  try {
+    int prio_least = 0, prio_greatest = 0;
+    RVN_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    for (int b = 0; b < 8; ++b) {
+      hipStream_t& st2 = b < 5 ? streams[b] : side[b - 5];
+      if (b >= 3 && prio_greatest != prio_least) RVN_HIP(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, prio_greatest));
+      else RVN_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
+    }
+    for (hipEvent_t& x : ev) RVN_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    for (hipEvent_t& x : side_ev) RVN_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  } catch (...) {
+    close();
+    throw;
+  }
+}
+void NwState::close() {
+  auto drop = [](auto& all, auto destroy) {
+    for (auto& x : all) {
+      if (x) (void)destroy(x);
+      x = nullptr;
+    }
+  };
+  drop(ev, hipEventDestroy);
+  drop(streams, hipStreamDestroy);
+  drop(side_ev, hipEventDestroy);
+  drop(side, hipStreamDestroy);
+}
+
 // Schedule: the jobs of a pass go in chunks whose hs + ck fit half the budget, longest jobs first.  The sweeps run on the
 // engine's stream, the walk of chunk i on a second stream beside the sweeps of chunk i + 1 (two buffer sets): a walk is
 // one lane per alignment and latency-bound (~1 us per column), a sweep fills the VALUs — together they cost the time of
@@ -331,55 +368,21 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   if (n_recs) RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
   if (nj == 0) return;
   RVN_HIP(hipEventRecord(e.ev0, s));
-  if (!e.nw_streams[0]) {
-    // HIP multiplexes its streams over a handful of hardware queues (four by default): two walk streams that land on the
-    // same queue run one after the other, and the ~100-ms walk of the longest alignments held the walk queued behind it —
-    // and with it the sweep waiting for that walk's buffer set (profiles/r05_nw_timeline.csv: a walk starting the moment
-    // the long one ended).  Streams of another PRIORITY get hardware queues of their own: the long pole's stream (set 3)
-    // is created at the highest priority, which also suits a kernel of 38 latency-bound waves.
-    int prio_least = 0, prio_greatest = 0;
-    RVN_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-    // created into locals and handed to the engine only when all exist: a creation that throws half-way must not leave
-    // nw_streams[0] set with the others null — the next call would skip this block and launch walks on the null stream
-    constexpr int kNwEv = static_cast<int>(sizeof(e.nw_ev) / sizeof(e.nw_ev[0]));
-    hipStream_t made[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [5..7]: nw_side
-    hipEvent_t made_ev[kNwEv + 4] = {};
-    try {
-      for (int b = 0; b < 8; ++b) {
-        // ([4], the upload stream, must not share a hardware queue with the engine's stream either: its copies run while a
-        // pass queued before is sweeping there)
-        if (b >= 3 && prio_greatest != prio_least)
-          RVN_HIP(hipStreamCreateWithPriority(&made[b], hipStreamNonBlocking, prio_greatest));
-        else
-          RVN_HIP(hipStreamCreateWithFlags(&made[b], hipStreamNonBlocking));
-      }
-      for (hipEvent_t& ev : made_ev) RVN_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    } catch (...) {
-      for (hipStream_t st2 : made)
-        if (st2) (void)hipStreamDestroy(st2);
-      for (hipEvent_t ev : made_ev)
-        if (ev) (void)hipEventDestroy(ev);
-      throw;
-    }
-    for (int b = 0; b < 3; ++b) e.nw_side[b] = made[5 + b];
-    for (int i = 0; i < 4; ++i) e.nw_side_ev[i] = made_ev[kNwEv + i];
-    for (int i = 0; i < kNwEv; ++i) e.nw_ev[i] = made_ev[i];
-    for (int b = 0; b < 5; ++b) e.nw_streams[b] = made[b];  // (last: what the test above looks at)
-  }
+  if (!e.nw.streams[0]) e.nw.open();
   // an error in the middle of a pass (a walk that left its band, an allocation that failed) must not leave walks running
   // on the side streams against buffers the next call hands out again
   struct WalkGuard {
     Engine& e;
     ~WalkGuard() {
       if (!std::uncaught_exceptions()) return;
-      for (hipStream_t st2 : e.nw_streams)
+      for (hipStream_t st2 : e.nw.streams)
         if (st2) (void)hipStreamSynchronize(st2);
-      for (hipStream_t st2 : e.nw_side)
+      for (hipStream_t st2 : e.nw.side)
         if (st2) (void)hipStreamSynchronize(st2);
       (void)hipStreamSynchronize(e.stream);
     }
   } walk_guard{e};
-  double rate = e.nw_rate > 0 ? e.nw_rate : 0.13;  // first call: ONT-like; too small only costs a repeat
+  double rate = e.nw.rate > 0 ? e.nw.rate : 0.13;  // first call: ONT-like; too small only costs a repeat
   if (const char* ev = knob("RVN_NW_RATE")) rate = std::atof(ev);  // (debug builds: force repeats)
   u64 budget = 0;
   // engine option nw_stripe_lanes: the widest ring of one sweep (variants with wider rings are skipped) = the stripe size
@@ -424,7 +427,8 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   {
     size_t free_b = 0, total_b = 0;
     RVN_HIP(hipMemGetInfo(&free_b, &total_b));
-    const u64 held = e.nw_hs.cap + e.nw_ck.cap + e.nw_hs2.cap + e.nw_ck2.cap + e.nw_hs3.cap + e.nw_ck3.cap + e.nw_hs4.cap + e.nw_ck4.cap;
+    u64 held = 0;
+    for (const NwState::Set& set : e.nw.sets) held += set.hs.cap + set.ck.cap;
     budget = std::min<u64>((static_cast<u64>(free_b) + devpool::free_total()) / 4 + held, 64ULL << 30);  // parked blocks count as free
     if (e.opt.nw_budget_mb > 0) budget = static_cast<u64>(e.opt.nw_budget_mb) << 20;
     budget = std::max<u64>(budget, 64ULL << 20);
@@ -439,8 +443,8 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   rates.reserve(nj);  // (growing it inside collect() cost milliseconds of page faults with the GPU idle)
   std::vector<u32> h_result(nj), h_status(nj);
   constexpr u32 kHeadMax = 4096;  // jobs of the pass of the longest alignments (below)
-  NwJob* d_jobs = e.nw_jobs.get<NwJob>(static_cast<size_t>(nj) + 1 + 2 * kHeadMax);
-  u32* d_res = e.nw_res.get<u32>(3 * static_cast<size_t>(nj) + 32 + 6 * kHeadMax);
+  NwJob* d_jobs = e.nw.jobs.get<NwJob>(static_cast<size_t>(nj) + 1 + 2 * kHeadMax);
+  u32* d_res = e.nw.res.get<u32>(3 * static_cast<size_t>(nj) + 32 + 6 * kHeadMax);
   u32* d_status = d_res + nj + 1;
   u32* d_idx = d_status + nj + 1;
   u32* d_next = d_idx + nj + 1;
@@ -459,7 +463,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   bool side_pending[3] = {false, false, false};   // sweeps on a side stream that the main stream has not waited for yet
   auto join_side = [&]() {
     for (int x = 0; x < 3; ++x) {
-      if (side_pending[x]) RVN_HIP(hipStreamWaitEvent(s, e.nw_side_ev[x], 0));
+      if (side_pending[x]) RVN_HIP(hipStreamWaitEvent(s, e.nw.side_ev[x], 0));
       side_pending[x] = false;
     }
   };
@@ -475,8 +479,6 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     u64 hs_w, ck_e;
     u32 coff[kClasses + 1];
   };
-  DevBuf* hs_buf[4] = {&e.nw_hs, &e.nw_hs2, &e.nw_hs3, &e.nw_hs4};
-  DevBuf* ck_buf[4] = {&e.nw_ck, &e.nw_ck2, &e.nw_ck3, &e.nw_ck4};
   bool set_used[4] = {false, false, false, false};  // a walk queued since the last collect() holds the buffer set
   struct Queued {  // what collect() reads back
     std::vector<u32> order;
@@ -599,14 +601,14 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         set_ck = std::max(set_ck, chunks[ci].ck_e);
       }
       if (!used) continue;
-      (void)hs_buf[b]->get<u32>(set_hs + 4 * 64 * 8 + 16);  // + slack: the walk reads up to two words past a job's last one
-      (void)ck_buf[b]->get<NwPm>(set_ck + 16);
+      (void)e.nw.sets[b].hs.get<u32>(set_hs + 4 * 64 * 8 + 16);  // + slack: the walk reads up to two words past a job's last one
+      (void)e.nw.sets[b].ck.get<NwPm>(set_ck + 16);
     }
     u64* d_strip = nullptr;
     if (!trace_lds) {
       size_t mc = 0;
       for (const Chunk& C : chunks) mc = std::max(mc, C.c1 - C.c0);
-      d_strip = e.nw_strip.get<u64>(static_cast<size_t>((mc + 63) / 64) * 2 * kNwStripCols * 64 * 4 + 64);
+      d_strip = e.nw.strip.get<u64>(static_cast<size_t>((mc + 63) / 64) * 2 * kNwStripCols * 64 * 4 + 64);
     }
     u32* d_slots = nullptr;
     if (path && !sweep_only) {
@@ -635,19 +637,19 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
       const Chunk& C = chunks[ci];
       const int b = set_of(ci);
-      u32* hs = hs_buf[b]->as<u32>();
-      NwPm* ck = ck_buf[b]->as<NwPm>();
+      u32* hs = e.nw.sets[b].hs.as<u32>();
+      NwPm* ck = e.nw.sets[b].ck.as<NwPm>();
       const u32* idx_c = dev.idx + C.c0;
       const u32 cn = static_cast<u32>(C.c1 - C.c0);
       // the walk that used this buffer set before (three chunks back in the rotation) is done with it
-      if (set_used[b]) RVN_HIP(hipStreamWaitEvent(s, e.nw_ev[b], 0));
+      if (set_used[b]) RVN_HIP(hipStreamWaitEvent(s, e.nw.ev[b], 0));
       auto count_of = [&](u32 x) -> u32 {  // classes are laid out from the widest variant down
         const u32 next_off = x == 0 ? cn : C.coff[x - 1];
         return next_off - C.coff[x];
       };
       // one walk stream per buffer set: the walk of the longest alignments (chunk 0: few waves, tens of milliseconds of
       // latency) must not hold back the walks of the chunks behind it
-      hipStream_t ts = one_stream ? s : e.nw_streams[b];
+      hipStream_t ts = one_stream ? s : e.nw.streams[b];
       auto launch_walk_to = [&](auto* d_out, hipStream_t wst, const u32* idx_w, u32 n_w) {
         using Out = typename std::remove_pointer<decltype(d_out)>::type;  // NwWindowRec: polishing; u32: the path form's slots
         if (group_walk == 2 || (group_walk != 1 && n_w <= kNwGroupWalkMaxJobs)) {
@@ -671,7 +673,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
           RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<false, kNwCkSteps, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
                                                  dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
                                                  dev.status, w, d_out,
-                                                 d_strip + static_cast<size_t>(b) * ((e.nw_strip.cap / 32) & ~size_t(63)))));
+                                                 d_strip + static_cast<size_t>(b) * ((e.nw.strip.cap / 32) & ~size_t(63)))));
         }
       };
       auto launch_walk = [&](hipStream_t wst, const u32* idx_w, u32 n_w) {
@@ -694,9 +696,9 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
             if (side[x]) side_used[x % 3] = true;
           }
         if (side_used[0] || side_used[1] || side_used[2]) {
-          RVN_HIP(hipEventRecord(e.nw_side_ev[3], s));
+          RVN_HIP(hipEventRecord(e.nw.side_ev[3], s));
           for (int y = 0; y < 3; ++y)
-            if (side_used[y]) RVN_HIP(hipStreamWaitEvent(e.nw_side[y], e.nw_side_ev[3], 0));
+            if (side_used[y]) RVN_HIP(hipStreamWaitEvent(e.nw.side[y], e.nw.side_ev[3], 0));
         }
       }
       if (const u32 n_str = count_of(kStriped)) {
@@ -718,7 +720,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       }
 #define RVN_SWEEP(x, R_, G_)                                                                                         \
   do {                                                                                                               \
-    launch_sweep<R_, G_>(e, side[x] ? e.nw_side[(x) % 3] : s, dev.jobs, idx_c + C.coff[x], count_of(x), T, Rd, hs, ck, \
+    launch_sweep<R_, G_>(e, side[x] ? e.nw.side[(x) % 3] : s, dev.jobs, idx_c + C.coff[x], count_of(x), T, Rd, hs, ck, \
                          dev.res, dev.status, side[x] ? d_side_next + (x) : d_next);                                   \
     if (dbg_sync && count_of(x)) {                                                                                   \
       RVN_HIP(hipStreamSynchronize(s));                                                                              \
@@ -736,20 +738,20 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
 #undef RVN_SWEEP
       for (int y = 0; y < 3; ++y)
         if (side_used[y]) {
-          RVN_HIP(hipEventRecord(e.nw_side_ev[y], e.nw_side[y]));
+          RVN_HIP(hipEventRecord(e.nw.side_ev[y], e.nw.side[y]));
           side_pending[y] = true;
         }
       ++st.n_batches;
       if (sweep_only) continue;
       if (!one_stream) {
-        RVN_HIP(hipEventRecord(e.nw_ev[4], s));
-        RVN_HIP(hipStreamWaitEvent(ts, e.nw_ev[4], 0));
+        RVN_HIP(hipEventRecord(e.nw.ev[4], s));
+        RVN_HIP(hipStreamWaitEvent(ts, e.nw.ev[4], 0));
         for (int y = 0; y < 3; ++y)
-          if (side_used[y]) RVN_HIP(hipStreamWaitEvent(ts, e.nw_side_ev[y], 0));
+          if (side_used[y]) RVN_HIP(hipStreamWaitEvent(ts, e.nw.side_ev[y], 0));
       }
       launch_walk(ts, idx_c, cn);
       if (!one_stream) {
-        RVN_HIP(hipEventRecord(e.nw_ev[b], ts));
+        RVN_HIP(hipEventRecord(e.nw.ev[b], ts));
         set_used[b] = true;
       }
       if (dbg_sync) {
@@ -765,7 +767,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     again.clear();
     join_side();
     for (int b = 0; b < 4; ++b) {  // (an event stands for the LAST walk recorded on its set)
-      if (set_used[b]) RVN_HIP(hipStreamWaitEvent(s, e.nw_ev[b], 0));
+      if (set_used[b]) RVN_HIP(hipStreamWaitEvent(s, e.nw.ev[b], 0));
       set_used[b] = false;
     }
     for (Queued& q : queued) {
@@ -876,8 +878,8 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     std::vector<u32> left;
     // (set 3 may have to grow for a doubled band, and growing hands the old block back: the walk on it — the head's, queued
     // long before — must be through)
-    if (set_used[3]) RVN_HIP(hipEventSynchronize(e.nw_ev[3]));
-    enqueue(todo, false, kHeadOnly, dev_retry, e.nw_streams[4], &left);
+    if (set_used[3]) RVN_HIP(hipEventSynchronize(e.nw.ev[3]));
+    enqueue(todo, false, kHeadOnly, dev_retry, e.nw.streams[4], &left);
     for (u32 i : left) early[i] = 0;  // (beyond the set's share: their doubled plan stands, collect() doubles it once more)
     st.n_retries -= left.size();
   };
@@ -1004,7 +1006,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     }
     ok.insert(ok.end(), left.begin(), left.end());
     h_plan += since(t_h);
-    enqueue(ok, false, split ? kRotating : kOwnFirst, dev_all, split ? e.nw_streams[4] : s, nullptr);
+    enqueue(ok, false, split ? kRotating : kOwnFirst, dev_all, split ? e.nw.streams[4] : s, nullptr);
     retry_early();
     std::vector<u32> again;
     collect(again);
@@ -1014,7 +1016,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   if (rates.size() >= 32) {  // rate estimate for the next call (the pilot's first threshold / small batches)
     const size_t at = std::min(rates.size() - 1, static_cast<size_t>(rates.size() * 0.9));
     std::nth_element(rates.begin(), rates.begin() + at, rates.end());  // (the order statistic a full sort gave: ~15 ms of host time per round)
-    e.nw_rate = rates[at] * 1.05 + 0.002;
+    e.nw.rate = rates[at] * 1.05 + 0.002;
   }
   RVN_HIP(hipEventSynchronize(e.ev1));
   float ms = 0;
@@ -1141,14 +1143,14 @@ void nw_align_paths(Engine& e, const ReadsDev& T, const ReadsDev& Q, std::vector
   RVN_HIP(hipMemcpyAsync(d_end, slots.slot_end.data(), (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice, s));
   RVN_HIP(hipMemcpyAsync(d_synth, synth.data(), (static_cast<size_t>(n) + 1) * 4, hipMemcpyHostToDevice, s));
   RVN_KLAUNCH(kKNwTraceback, nw_path_count_kernel<<<n / 256 + 1, 256, 0, s>>>(d_end, d_synth, n, d_cnt));
-  exclusive_scan_u32_u64(d_cnt, d_run_off, static_cast<u64>(n) + 1, e.scan_tmp, s);
+  exclusive_scan_u32_u64(d_cnt, d_run_off, static_cast<u64>(n) + 1, e.scratch.scan_tmp, s);
   u64 total = 0;
   RVN_HIP(hipMemcpyAsync(&total, d_run_off + n, 8, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));  // (also: `synth` and the slot addresses are pageable)
   out.n_runs = total;
   u32* d_runs = out.runs.get<u32>(static_cast<size_t>(total) + 1);
   RVN_KLAUNCH(kKNwTraceback, nw_path_pack_kernel<<<n / 4 + 1, 256, 0, s>>>(d_end, d_synth, d_run_off, n, d_runs, d_cnt));
-  exclusive_scan_u32_u64(d_cnt, d_op_off, static_cast<u64>(n) + 1, e.scan_tmp, s);
+  exclusive_scan_u32_u64(d_cnt, d_op_off, static_cast<u64>(n) + 1, e.scratch.scan_tmp, s);
   RVN_HIP(hipMemcpyAsync(&total, d_op_off + n, 8, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipEventRecord(e.ev1, s));
   RVN_HIP(rvn_stream_sync(s));  // (the slots go back when this returns)

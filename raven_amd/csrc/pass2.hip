@@ -180,7 +180,7 @@ __global__ void merge_invalid_kernel(PileRegion* __restrict__ regions, const u8*
 KeptSlots kept_slots(Engine& e, const u8* d_keep, u64 n, DevBuf& slot) {
   if (n == 0) return {nullptr, 0};
   u32* d_slot = slot.get<u32>(n + 2);
-  exclusive_scan_u8_u32(d_keep, d_slot, n, e.scan_tmp, e.stream);
+  exclusive_scan_u8_u32(d_keep, d_slot, n, e.scratch.scan_tmp, e.stream);
   return {d_slot, read_back(e, d_slot + n, 4)};
 }
 
@@ -207,13 +207,13 @@ void update_and_identity(Engine& e, const ReadsDev& r, Overlap* d_ovl, u64 n, co
   update_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, n, d_regions, d_ok);
   RVN_LAUNCH_CHECK();
   if (identity == 0) return;
-  const KeptSlots ks = kept_slots(e, d_ok, n, e.p2_slot);
+  const KeptSlots ks = kept_slots(e, d_ok, n, e.p2.slot);
   const u32* d_slot = ks.slot;
   const u64 np = ks.kept;
   if (np == 0) return;
   if (np >= 0xFFFFFFFFULL) throw std::invalid_argument("[raven_hip] identity filter: too many pairs in one batch");
-  EdPairRec* d_pairs = e.p2_pairs.get<EdPairRec>(np + 1);
-  u32* d_dist = e.p2_dist.get<u32>(2 * (np + 1));
+  EdPairRec* d_pairs = e.p2.pairs.get<EdPairRec>(np + 1);
+  u32* d_dist = e.p2.dist.get<u32>(2 * (np + 1));
   u32* d_kmax = d_dist + np + 1;
   ed_pairs_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, d_ok, d_slot, n, d_index_of, identity, d_pairs, d_kmax);
   RVN_LAUNCH_CHECK();
@@ -251,7 +251,7 @@ void reads_subset(Engine& e, const ReadsDev& R, const std::vector<u32>& src, Rea
   u64* d_wo = V.word_off.get<u64>(static_cast<size_t>(n) + 1);
   u32* d_len = V.len.get<u32>(static_cast<size_t>(n) + 1);
   u32* d_id = V.id.get<u32>(static_cast<size_t>(n) + 1);
-  u32* d_src = e.p2_slot.get<u32>(static_cast<size_t>(n) + 2);
+  u32* d_src = e.p2.slot.get<u32>(static_cast<size_t>(n) + 2);
   RVN_HIP(hipMemcpyAsync(d_wo, V.h_word_off.data(), (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice, s));
   if (n) {
     RVN_HIP(hipMemcpyAsync(d_len, V.h_len.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, s));
@@ -294,7 +294,7 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
   out.n = n;
   out.n_overlaps = 0;
   P.batches.clear();
-  P.d_regions = upload_pile_regions(e, e.p2_regions, h_begin, h_end, h_invalid, n);
+  P.d_regions = upload_pile_regions(e, e.p2.regions, h_begin, h_end, h_invalid, n);
   u8* d_contained = out.contained.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemsetAsync(d_contained, 0, static_cast<size_t>(n) + 16, s));
   // valid reads first, by id (construct.cc:324-349); index_of: id -> position among the valid reads
@@ -329,8 +329,8 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
   }
   const u32 sv = P.sv;
   reads_subset(e, R, P.valid, P.V);
-  P.d_index_of = upload(e.p2_index_of, index_of.data(), n, s);
-  P.d_v_kmers_off = upload(e.p2_kmers_off, P.h_v_kmers_off.data(), static_cast<size_t>(sv) + 1, s);
+  P.d_index_of = upload(e.p2.index_of, index_of.data(), n, s);
+  P.d_v_kmers_off = upload(e.p2.kmers_off, P.h_v_kmers_off.data(), static_cast<size_t>(sv) + 1, s);
   RVN_HIP(rvn_stream_sync(s));
   // index batches of batch_bases valid bases: [first, last) of the valid reads
   u64 bytes = 0;
@@ -353,26 +353,26 @@ u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first,
   const ReadsDev& V = P.V;
   engine_minimize(e, V, first, last, false);
   index_filter(e, freq);
-  MapOut& mo = e.map_out;
+  MapOut& mo = e.map.out;
   map_batch(e, V, q_first, q_last, true, true, false, true, mo);
   e.c_intervals += mo.n_intervals;
   // Pile::AddKmers(filtered, kmer_len, sequence) of every mapped read (construct.cc:382)
   if (mo.n_query) {
     RVN_KLAUNCH(kKAddKmers, add_kmers_flags_kernel<<<div_up(mo.n_query, 256), 256, 0, s>>>(
                                 V.packed.as<u64>(), V.word_off.as<u64>() + q_first, mo.filtered.as<u8>(),
-                                e.query_sketch.org.as<u64>(), e.query_sketch.read_off.as<u32>(), q_last - q_first, mo.n_query,
+                                e.sketch.query_sketch.org.as<u64>(), e.sketch.query_sketch.read_off.as<u32>(), q_last - q_first, mo.n_query,
                                 kmer_len, P.d_v_kmers_off + q_first, out.kmers.as<u8>()));
   }
   const u64 O = mo.n_overlaps;
   if (O == 0) return 0;
   const u64 acc_n = out.n_overlaps;
   Overlap* d_ovl = mo.ovl.as<Overlap>();
-  u8* d_ok = e.p2_ok.get<u8>(O + 16);
-  u8* d_keep = e.p2_keep.get<u8>(O + 16);
+  u8* d_ok = e.p2.ok.get<u8>(O + 16);
+  u8* d_keep = e.p2.keep.get<u8>(O + 16);
   update_and_identity(e, V, d_ovl, O, P.d_regions, P.d_index_of, identity, d_ok);
   classify_kernel<<<div_up(O, 256), 256, 0, s>>>(d_ovl, d_ok, O, P.d_regions, out.contained.as<u8>(), d_keep);
   RVN_LAUNCH_CHECK();
-  const KeptSlots ks = kept_slots(e, d_keep, O, e.p2_slot);
+  const KeptSlots ks = kept_slots(e, d_keep, O, e.p2.slot);
   const u64 m = ks.kept;
   if (m == 0) return 0;
   // append to the result list
@@ -388,21 +388,21 @@ void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out) {
   hipStream_t s = e.stream;
   u64 acc_n = out.n_overlaps;
   if (acc_n) {
-    u8* d_keep = e.p2_keep.get<u8>(acc_n + 16);
+    u8* d_keep = e.p2.keep.get<u8>(acc_n + 16);
     RVN_HIP(hipMemsetAsync(d_keep, 1, acc_n, s));
     dedup_kernel<<<div_up(acc_n, 256), 256, 0, s>>>(out.ovl.as<Overlap>(), acc_n, d_keep);
     RVN_LAUNCH_CHECK();
-    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_keep, e.p2_slot, e.p2_tmp_ovl);
+    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_keep, e.p2.slot, e.p2.tmp_ovl);
   }
   if (out.n) {
     merge_invalid_kernel<<<div_up(out.n, 256), 256, 0, s>>>(d_regions, out.contained.as<u8>(), out.n);
     RVN_LAUNCH_CHECK();
   }
   if (acc_n) {
-    u8* d_ok = e.p2_ok.get<u8>(acc_n + 16);
+    u8* d_ok = e.p2.ok.get<u8>(acc_n + 16);
     update_kernel<<<div_up(acc_n, 256), 256, 0, s>>>(out.ovl.as<Overlap>(), acc_n, d_regions, d_ok);
     RVN_LAUNCH_CHECK();
-    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_ok, e.p2_slot, e.p2_tmp_ovl);
+    acc_n = compact_overlap_list(e, out.ovl, acc_n, d_ok, e.p2.slot, e.p2.tmp_ovl);
   }
   RVN_HIP(rvn_stream_sync(s));
   out.n_overlaps = acc_n;
@@ -424,9 +424,9 @@ void identity_filter_flags(Engine& e, const ReadsDev& R, const Overlap* h_ovl, u
                            const u8* h_invalid, double identity, u8* h_ok, Overlap* h_upd) {
   hipStream_t s = e.stream;
   if (O == 0) return;
-  PileRegion* d_regions = upload_pile_regions(e, e.p2_regions, h_begin, h_end, h_invalid, R.n);
-  Overlap* d_ovl = upload(e.p2_tmp_ovl, h_ovl, O, s);
-  u8* d_ok = e.p2_ok.get<u8>(O + 16);
+  PileRegion* d_regions = upload_pile_regions(e, e.p2.regions, h_begin, h_end, h_invalid, R.n);
+  Overlap* d_ovl = upload(e.p2.tmp_ovl, h_ovl, O, s);
+  u8* d_ok = e.p2.ok.get<u8>(O + 16);
   update_and_identity(e, R, d_ovl, O, d_regions, nullptr, identity, d_ok);  // ids are indices
   RVN_HIP(hipMemcpyAsync(h_ok, d_ok, O, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(h_upd, d_ovl, O * sizeof(Overlap), hipMemcpyDeviceToHost, s));

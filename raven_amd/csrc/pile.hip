@@ -241,10 +241,10 @@ void pile_add_kmers_batch(Engine& e, const ReadsDev& r, const u32* h_pos, const 
   std::vector<u64> off(static_cast<size_t>(r.n) + 1, 0);
   for (u32 i = 0; i < n_reads; ++i) off[first_read + i] = h_out_off[i];
   const u64 out_total = h_out_off[n_reads];
-  u32* d_pos = e.tmp_a.get<u32>(n + 1);
-  u32* d_pr = e.tmp_b.get<u32>(n + 1);
-  u64* d_off = e.tmp_c.get<u64>(off.size() + 1);
-  u8* d_out = e.tmp_d.get<u8>(out_total + 16);
+  u32* d_pos = e.scratch.tmp_a.get<u32>(n + 1);
+  u32* d_pr = e.scratch.tmp_b.get<u32>(n + 1);
+  u64* d_off = e.scratch.tmp_c.get<u64>(off.size() + 1);
+  u8* d_out = e.scratch.tmp_d.get<u8>(out_total + 16);
   RVN_HIP(hipMemcpyAsync(d_pos, h_pos, n * 4, hipMemcpyHostToDevice, s));
   RVN_HIP(hipMemcpyAsync(d_pr, pos_read.data(), n * 4, hipMemcpyHostToDevice, s));
   RVN_HIP(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
@@ -286,14 +286,14 @@ void piles_merge(Engine& e, const ReadsDev& r, const MapOut& mo, u32 kmax, PileS
       *new_kept_cnt = base + 4 * stride, *new_kept_off = base + 5 * stride;
   RVN_HIP(hipMemsetAsync(in_cnt, 0, stride * 4, s));
   RVN_KLAUNCH(kKPileKeys, rhs_keys_kernel<<<div_up(O, 256), 256, 0, s>>>(ovl, O, keys0, idx0, in_cnt));
-  const int cur = radix_sort_pairs_u32_u32(keys0, keys1, idx0, idx1, O, 32, e.sort_tmp, e.scan_tmp, s, kKPileSortUp,
+  const int cur = radix_sort_pairs_u32_u32(keys0, keys1, idx0, idx1, O, 32, e.scratch.sort_tmp, e.scratch.scan_tmp, s, kKPileSortUp,
                                            kKPileSortDown);
   const u32* in_idx_sorted = cur ? idx1 : idx0;
-  exclusive_scan_u32_u32(in_cnt, in_off, n, e.scan_tmp, s);
+  exclusive_scan_u32_u32(in_cnt, in_off, n, e.scratch.scan_tmp, s);
   RVN_KLAUNCH(kKPileCounts, pile_counts_kernel<<<div_up(n, 256), 256, 0, s>>>(in_cnt, ovl_read_off, mo.first, mo.last, ps.kept_off.as<u32>(), n,
                                                     kmax, tot, new_kept_cnt));
-  exclusive_scan_u32_u32(tot, list_off, n, e.scan_tmp, s);
-  exclusive_scan_u32_u32(new_kept_cnt, new_kept_off, n, e.scan_tmp, s);
+  exclusive_scan_u32_u32(tot, list_off, n, e.scratch.scan_tmp, s);
+  exclusive_scan_u32_u32(new_kept_cnt, new_kept_off, n, e.scratch.scan_tmp, s);
   RVN_HIP(hipMemcpyAsync(e.h_pin, list_off + n, 4, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(e.h_pin + 1, new_kept_off + n, 4, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
@@ -640,10 +640,10 @@ u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, D
     RVN_HIP(rvn_stream_sync(s));
     return 0;
   }
-  SlopeRegion* d_slopes = e.tmp_b.get<SlopeRegion>(2 * ps.pile_words + 2);
-  u16* d_tmp = e.tmp_c.get<u16>(ps.pile_words + 1);
-  u32* d_out = e.tmp_d.get<u32>(2 * ps.pile_words + 4);
-  u32* d_cnt = e.tmp_e.get<u32>(static_cast<size_t>(n) + 16);
+  SlopeRegion* d_slopes = e.scratch.tmp_b.get<SlopeRegion>(2 * ps.pile_words + 2);
+  u16* d_tmp = e.scratch.tmp_c.get<u16>(ps.pile_words + 1);
+  u32* d_out = e.scratch.tmp_d.get<u32>(2 * ps.pile_words + 4);
+  u32* d_cnt = e.scratch.tmp_e.get<u32>(static_cast<size_t>(n) + 16);
   u32* d_ovf = d_cnt + n + 8;
   RVN_HIP(hipMemsetAsync(d_ovf, 0, 4, s));
   if (kernel == kChimericByKnob) kernel = knob("RVN_CHIMERIC_PER_THREAD") ? kChimericPerThread : kChimericWave;
@@ -653,7 +653,7 @@ u32 piles_find_chimeric_regions_dev(Engine& e, PileState& ps, const u8* d_inv, D
   else
     RVN_KLAUNCH(kKPileTrim, pile_chimeric_wave_kernel<<<n, 64, 0, s>>>(ps.pile_data.as<u16>(), ps.pile_off.as<u64>(), d_inv, n,
                                                                       d_slopes, d_tmp, d_out, d_cnt, d_ovf));
-  exclusive_scan_u32_u32(d_cnt, d_roff, n, e.scan_tmp, s);
+  exclusive_scan_u32_u32(d_cnt, d_roff, n, e.scratch.scan_tmp, s);
   RVN_HIP(hipMemcpyAsync(e.h_pin + 1, d_roff + n, 4, hipMemcpyDeviceToHost, s));
   if (read_back(e, d_ovf, 4) != 0)
     throw HipError("[raven_hip] FindChimericRegions: a pile produced more than two slope regions per cell (internal error: the bound in pile.hip is a proof)");
@@ -674,12 +674,12 @@ void piles_find_chimeric_regions(Engine& e, PileState& ps, const u8* h_invalid, 
   h_off.assign(static_cast<size_t>(n) + 1, 0);
   h_regions.clear();
   if (n == 0 || ps.pile_words == 0) return;
-  u8* d_inv = e.tmp_a.get<u8>(static_cast<size_t>(n) + 16);
+  u8* d_inv = e.scratch.tmp_a.get<u8>(static_cast<size_t>(n) + 16);
   RVN_HIP(hipMemcpyAsync(d_inv, h_invalid, n, hipMemcpyHostToDevice, s));
-  const u32 total = piles_find_chimeric_regions_dev(e, ps, d_inv, e.tmp_f, e.sort_tmp, kernel);
-  RVN_HIP(hipMemcpyAsync(h_off.data(), e.tmp_f.ptr, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToHost, s));
+  const u32 total = piles_find_chimeric_regions_dev(e, ps, d_inv, e.scratch.tmp_f, e.scratch.sort_tmp, kernel);
+  RVN_HIP(hipMemcpyAsync(h_off.data(), e.scratch.tmp_f.ptr, (static_cast<size_t>(n) + 1) * 4, hipMemcpyDeviceToHost, s));
   h_regions.assign(2ULL * total, 0);
-  if (total) RVN_HIP(hipMemcpyAsync(h_regions.data(), e.sort_tmp.ptr, 2ULL * total * 4, hipMemcpyDeviceToHost, s));
+  if (total) RVN_HIP(hipMemcpyAsync(h_regions.data(), e.scratch.sort_tmp.ptr, 2ULL * total * 4, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
 }
 

@@ -601,10 +601,10 @@ void poa_v1_launch(Engine& e, const PoaBatchDev& b) {
   size_t free_b = 0, total_b = 0;
   RVN_HIP(hipMemGetInfo(&free_b, &total_b));
   u32 n_slots = std::min<u32>(b.n_windows, 256 * 8);
-  const size_t budget = e.poa_scratch.cap + (free_b + devpool::free_total()) / 2;
+  const size_t budget = e.poa.scratch.cap + (free_b + devpool::free_total()) / 2;
   if (static_cast<size_t>(n_slots) * slot_bytes > budget) n_slots = static_cast<u32>(std::max<size_t>(1, budget / slot_bytes));
   n_slots = ((n_slots + 3) / 4) * 4;
-  unsigned char* d_scratch = e.poa_scratch.get<unsigned char>(static_cast<size_t>(n_slots) * slot_bytes + 256);
+  unsigned char* d_scratch = e.poa.scratch.get<unsigned char>(static_cast<size_t>(n_slots) * slot_bytes + 256);
   RVN_HIP(hipMemsetAsync(b.next, 0, 4, e.stream));
   RVN_KLAUNCH(kKPoa, poa_kernel<<<n_slots / 4, 256, 0, e.stream>>>(b.wins, b.n_windows, b.layers, b.src,
                                                                     d_scratch, slot_bytes, n_slots, b.nmax, b.lmax, b.m,
@@ -661,18 +661,18 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
   b.trim = trim;
   b.n_windows = n_windows;
   b.src = src;
-  unsigned long long* d_phase = e.q_start.get<unsigned long long>(16);  // [0..7] phases + cells, [8] work counter, [10..15] kernel statistics
+  unsigned long long* d_phase = e.map.q_start.get<unsigned long long>(16);  // [0..7] phases + cells, [8] work counter, [10..15] kernel statistics
   RVN_HIP(hipMemsetAsync(d_phase, 0, 128, s));
   // heaviest windows first: cost ~ number of layers
   const u32 esc_cap = std::min<u32>(n_windows, 1u << 16);
-  u32* d_sk = e.poa_sched.get<u32>(4 * static_cast<size_t>(n_windows) + 8 + esc_cap + 4);
+  u32* d_sk = e.poa.sched.get<u32>(4 * static_cast<size_t>(n_windows) + 8 + esc_cap + 4);
   u32* d_sk1 = d_sk + n_windows + 1;
   u32* d_sv = d_sk1 + n_windows + 1;
   u32* d_sv1 = d_sv + n_windows + 1;
   u32* d_esc = d_sv1 + n_windows + 1;
   poa_sched_keys_kernel<<<div_up(n_windows, 256), 256, 0, s>>>(d_wins, n_windows, d_sk, d_sv);
   RVN_LAUNCH_CHECK();
-  const int which = radix_sort_pairs_u32_u32(d_sk, d_sk1, d_sv, d_sv1, n_windows, 16, e.sort_tmp, e.scan_tmp, s,
+  const int which = radix_sort_pairs_u32_u32(d_sk, d_sk1, d_sv, d_sv1, n_windows, 16, e.scratch.sort_tmp, e.scratch.scan_tmp, s,
                                              kKPileSortUp, kKPileSortDown, false);
   b.sched = which ? d_sv1 : d_sv;
   b.next = reinterpret_cast<u32*>(d_phase + 8);
@@ -688,7 +688,7 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
   // parameters far beyond spoa's usual single digits go straight to the int32 full-matrix kernel
   const auto mag = [](int x) { return x < 0 ? -x : x; };
   const bool int16_ok = mag(m) <= 24 && mag(n) <= 24 && mag(g) <= 24;
-  const int mode = int16_ok ? e.poa_mode : 1;
+  const int mode = int16_ok ? e.poa.mode : 1;
   // first attempt: rows on lanes with a 32-column band (poa4.hip); mode 9 = poa4.hip alone.  A batch too small to fill the
   // chip with groups of four windows is faster in poa2's one-window-per-wave kernel (10 000 windows of a configs[2] round:
   // 108 ms in poa4's persistent kernel, 66 ms in poa2's; at 24 576 windows poa4 is ahead): below the threshold the default
@@ -730,17 +730,17 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
     }
     std::fprintf(stderr, " (cumulative share)\n");
   }
-  e.poa_fallback_windows = 0;
-  e.poa_narrow_windows = 0;
-  e.poa_wide_windows = esc_head[2];  // (windows that went through the 128-column function inside the first launch)
-  e.poa_fullmatrix_windows = 0;
+  e.poa.fallback_windows = 0;
+  e.poa.narrow_windows = 0;
+  e.poa.wide_windows = esc_head[2];  // (windows that went through the 128-column function inside the first launch)
+  e.poa.fullmatrix_windows = 0;
   if (mode == 0) {
     // escalate what the 64-column band could not do: band hits -> 128-column band -> 256 -> full matrix; windows
     // beyond a limit (nodes / in-degree / length) -> full matrix directly
     auto rerun = [&](const std::vector<u32>& redo, int which_kernel) {
       const u32 nr = static_cast<u32>(redo.size());
-      PoaWindow* d_rw = e.poa_redo_w.get<PoaWindow>(nr + 1);
-      u32* d_ridx = e.poa_redo_i.get<u32>(3 * static_cast<size_t>(nr) + 4);
+      PoaWindow* d_rw = e.poa.redo_w.get<PoaWindow>(nr + 1);
+      u32* d_ridx = e.poa.redo_i.get<u32>(3 * static_cast<size_t>(nr) + 4);
       u32* d_rlen = d_ridx + nr + 1;
       u32* d_rstatus = d_rlen + nr + 1;
       RVN_HIP(hipMemcpyAsync(d_ridx, redo.data(), nr * 4, hipMemcpyHostToDevice, s));
@@ -775,7 +775,7 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
         std::fprintf(stderr, "[raven_hip] poa: %zu of %u windows handed on by the first attempt: steps %u, in-degree %u, band step along an in-edge %u, last column outside the bands %u, walk near a band's edge %u, walk met a backpointer it cannot follow %u\n",
                      narrow.size(), n_windows, why[1], why[3], why[7], why[9], why[10], why[11]);
       if (!narrow.empty()) rerun(narrow, 64);
-      e.poa_narrow_windows = static_cast<u32>(narrow.size()) + esc_pushed;
+      e.poa.narrow_windows = static_cast<u32>(narrow.size()) + esc_pushed;
     }
     for (u32 w = 0; w < n_windows; ++w) {
       const u32 st = h_status[w] & 0xFF;
@@ -791,7 +791,7 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
     }
     if (!wide.empty()) {  // 128 columns
       rerun(wide, 2);
-      e.poa_wide_windows += static_cast<u32>(wide.size());
+      e.poa.wide_windows += static_cast<u32>(wide.size());
       for (u32 w : wide) {
         const u32 st = h_status[w] & 0xFF;
         if (st == kPoaBandHit) wider.push_back(w);
@@ -801,28 +801,28 @@ void poa_run_dev(Engine& e, const PoaWindow* d_wins, const PoaLayer* d_lays, u32
     const size_t direct_full = fullm.size();  // limits hit in the first two stages: not a matter of band width
     if (!wider.empty()) {  // 256 columns
       rerun(wider, 4);
-      e.poa_fallback_windows = static_cast<u32>(wider.size() + direct_full);
+      e.poa.fallback_windows = static_cast<u32>(wider.size() + direct_full);
       for (u32 w : wider)
         if ((h_status[w] & 0xFF) >= 2) fullm.push_back(w);
     }
-    if (wider.empty()) e.poa_fallback_windows = static_cast<u32>(direct_full);
+    if (wider.empty()) e.poa.fallback_windows = static_cast<u32>(direct_full);
     if (!fullm.empty() && allow_full) {
       rerun(fullm, 1);
-      e.poa_fullmatrix_windows = static_cast<u32>(fullm.size());
+      e.poa.fullmatrix_windows = static_cast<u32>(fullm.size());
     }
   }
   RVN_HIP(hipEventRecord(e.ev1, s));
-  RVN_HIP(hipMemcpyAsync(e.poa_phase_cycles, d_phase, 64, hipMemcpyDeviceToHost, s));
+  RVN_HIP(hipMemcpyAsync(e.poa.phase_cycles, d_phase, 64, hipMemcpyDeviceToHost, s));
   unsigned long long kstats[7] = {};
   const bool want_stats = knob("RVN_POA_STATS") != nullptr;
   if (want_stats) RVN_HIP(hipMemcpyAsync(kstats, d_phase + 9, 56, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
   if (want_stats)
     std::fprintf(stderr, "[raven_hip] poa kernel statistics (poa4.hip): descriptor-pass cycles %llu, traceback steps %llu round changes %llu (cycles in them %llu), dp wave-steps %llu (dp cycles %llu, in service points %llu), window set-up cycles %llu\n",
-                 kstats[1], kstats[2], kstats[3], kstats[4], kstats[5], e.poa_phase_cycles[1], kstats[0], kstats[6]);
-  e.poa_cells_full += e.poa_phase_cycles[6];
-  e.poa_cells_band += e.poa_phase_cycles[7];
-  e.poa_calls += 1;
+                 kstats[1], kstats[2], kstats[3], kstats[4], kstats[5], e.poa.phase_cycles[1], kstats[0], kstats[6]);
+  e.poa.cells_full += e.poa.phase_cycles[6];
+  e.poa.cells_band += e.poa.phase_cycles[7];
+  e.poa.calls += 1;
   if (device_ms) {
     float ms = 0;
     RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
@@ -837,10 +837,10 @@ void poa_run(Engine& e, const std::vector<PoaWindow>& wins, const std::vector<Po
   const u32 n_windows = static_cast<u32>(wins.size());
   if (n_windows == 0) return;
   hipStream_t s = e.stream;
-  PoaWindow* d_wins = e.tmp_c.get<PoaWindow>(static_cast<size_t>(n_windows) + 2);
-  PoaLayer* d_lays = e.tmp_d.get<PoaLayer>(lays.size() + 1);
-  u8* d_out = e.tmp_e.get<u8>(out_total + 16);
-  u32* d_len = e.tmp_f.get<u32>(2 * static_cast<size_t>(n_windows) + 4);
+  PoaWindow* d_wins = e.scratch.tmp_c.get<PoaWindow>(static_cast<size_t>(n_windows) + 2);
+  PoaLayer* d_lays = e.scratch.tmp_d.get<PoaLayer>(lays.size() + 1);
+  u8* d_out = e.scratch.tmp_e.get<u8>(out_total + 16);
+  u32* d_len = e.scratch.tmp_f.get<u32>(2 * static_cast<size_t>(n_windows) + 4);
   u32* d_status = d_len + n_windows + 1;
   RVN_HIP(hipMemcpyAsync(d_wins, wins.data(), wins.size() * sizeof(PoaWindow), hipMemcpyHostToDevice, s));
   RVN_HIP(hipMemcpyAsync(d_lays, lays.data(), lays.size() * sizeof(PoaLayer), hipMemcpyHostToDevice, s));
@@ -905,8 +905,8 @@ void poa_consensus_batch(Engine& e, const u8* h_codes, const u8* h_quals, const 
   u32 max_bb = 1, max_len = 1;
   poa_build_host_batch(h_layer_off, h_begins, h_ends, h_has_qual, h_quals != nullptr, h_win_off, n_windows, h_out_off, wins,
                        lays, max_bb, max_len);
-  u8* d_codes = e.tmp_a.get<u8>(total + 16);
-  u8* d_quals = h_quals ? e.tmp_b.get<u8>(total + 16) : nullptr;
+  u8* d_codes = e.scratch.tmp_a.get<u8>(total + 16);
+  u8* d_quals = h_quals ? e.scratch.tmp_b.get<u8>(total + 16) : nullptr;
   RVN_HIP(hipMemcpyAsync(d_codes, h_codes, total, hipMemcpyHostToDevice, s));
   if (d_quals) RVN_HIP(hipMemcpyAsync(d_quals, h_quals, total, hipMemcpyHostToDevice, s));
   PoaSrc src{};

@@ -2562,11 +2562,11 @@ void poa_v4_launch(Engine& e, const PoaBatchDev& b) {
   RVN_HIP(hipMemGetInfo(&free_b, &total_b));
   const size_t per_wave = P4::G * (slot_bytes + sizeof(Poa4Win));
   // (a buffer handed back to the block pool at a stage entry is still there for the taking)
-  const size_t budget = std::max(e.poa2_scratch.cap, devpool::free_largest()) + free_b / 2;
+  const size_t budget = std::max(e.poa.scratch2.cap, devpool::free_largest()) + free_b / 2;
   u32 n_waves = std::min<u32>(n_quads, static_cast<u32>(cus) * 16u);
   if (static_cast<size_t>(n_waves) * per_wave + 1024 > budget) n_waves = static_cast<u32>(std::max<size_t>(1, (budget - 1024) / per_wave));
   const size_t slots = static_cast<size_t>(n_waves) * P4::G;
-  unsigned char* d_scratch = e.poa2_scratch.get<unsigned char>(slots * (slot_bytes + sizeof(Poa4Win)) + 512);
+  unsigned char* d_scratch = e.poa.scratch2.get<unsigned char>(slots * (slot_bytes + sizeof(Poa4Win)) + 512);
   Poa4Win* d_st = reinterpret_cast<Poa4Win*>(d_scratch + slots * slot_bytes + 256);
   Poa4Args A = args_of4(b, d_scratch, slot_bytes);
   if (b.esc && poa2_slot_bytes(b.nmax, b.lmax, 64) <= P4::G * slot_bytes) {  // (the wave's four slots as the 64-column function's one)

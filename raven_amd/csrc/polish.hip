@@ -271,10 +271,10 @@ void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_las
   if (T.n == 0 || nr_all == 0) return;
   {
     StageTimer t(e, StageTimes::kSketch);
-    e.query_ready = false;
-    e.index.has_query_flags = false;
-    e.index.all_query = false;
-    sketch_raw(e, T, 0, T.n, e.index_sketch);
+    e.sketch.query_ready = {};
+    e.sketch.index.has_query_flags = false;
+    e.sketch.index.all_query = false;
+    sketch_raw(e, T, 0, T.n, e.sketch.index_sketch);
     t.stop();
   }
   // Option polish_join (round 6; VERDICT r03-r05: the probes' over-fetch — one random binary search + origin gather per read
@@ -285,21 +285,21 @@ void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_las
   // racon does.  Bit-identical to the probes and SLOWER at C4 (88 against 59 ms of kernels per round: sorting 1.1 G entries
   // costs what probing them costs) — hence an option, not the default.
   const bool joined = R.ids_are_indices && e.opt.polish_join != 0;
-  const u64 t_count = e.index_sketch.count;
+  const u64 t_count = e.sketch.index_sketch.count;
   const size_t vb = e.val64 ? 8 : 4;
   if (joined && t_count) {
-    RVN_HIP(hipMemcpyAsync(e.pl_tval.get<unsigned char>((t_count + 1) * vb), e.index_sketch.val.ptr, t_count * vb, hipMemcpyDeviceToDevice, s));
-    RVN_HIP(hipMemcpyAsync(e.pl_torg.get<u64>(t_count + 1), e.index_sketch.org.ptr, t_count * 8, hipMemcpyDeviceToDevice, s));
+    RVN_HIP(hipMemcpyAsync(e.polish.tval.get<unsigned char>((t_count + 1) * vb), e.sketch.index_sketch.val.ptr, t_count * vb, hipMemcpyDeviceToDevice, s));
+    RVN_HIP(hipMemcpyAsync(e.polish.torg.get<u64>(t_count + 1), e.sketch.index_sketch.org.ptr, t_count * 8, hipMemcpyDeviceToDevice, s));
   }
-  index_build(e, e.index_sketch, !joined);
+  index_build(e, e.sketch.index_sketch, !joined);
   index_filter(e, 0.001);
-  const u32 occurrence = e.index.occurrence;
+  const u32 occurrence = e.sketch.index.occurrence;
   u32 max_id = 0;
   for (u32 t = 0; t < T.n; ++t) max_id = std::max(max_id, T.h_id[t]);
   {
     std::vector<u32> id_to_t(static_cast<size_t>(max_id) + 1, 0xFFFFFFFFu);
     for (u32 t = 0; t < T.n; ++t) id_to_t[T.h_id[t]] = t;
-    u32* d = e.pl_idmap.get<u32>(id_to_t.size());
+    u32* d = e.polish.idmap.get<u32>(id_to_t.size());
     RVN_HIP(hipMemcpyAsync(d, id_to_t.data(), id_to_t.size() * 4, hipMemcpyHostToDevice, s));
     RVN_HIP(rvn_stream_sync(s));
   }
@@ -317,10 +317,10 @@ void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_las
     a.org.swap(b.org);
     a.read_off.swap(b.read_off);
   };
-  Overlap* d_best = e.pl_best.get<Overlap>(static_cast<size_t>(R.n) + 1);
-  u32* d_best_t = e.pl_best_t.get<u32>(static_cast<size_t>(R.n) + 1);
-  const bool keep = e.keep_anchors;
-  e.keep_anchors = false;
+  Overlap* d_best = e.polish.best.get<Overlap>(static_cast<size_t>(R.n) + 1);
+  u32* d_best_t = e.polish.best_t.get<u32>(static_cast<size_t>(R.n) + 1);
+  const bool keep = e.map.keep_anchors;
+  e.map.keep_anchors = false;
   try {
     // racon maps its reads in batches of about 1 GB; the match / overlap memory of a round is that of one batch
     u64 bases = 0;
@@ -328,80 +328,77 @@ void polish_map_best(Engine& e, ReadsDev& T, ReadsDev& R, u32 r_first, u32 r_las
       bases += R.h_len[r];
       if (r != r_last - 1 && bases < (1ULL << 30)) continue;
       bases = 0;
-      MapOut& mo = e.map_out;
+      MapOut& mo = e.map.out;
       if (joined && t_count) {
         {
           StageTimer t(e, StageTimes::kQuery);
-          sketch_raw(e, R, r0, r + 1, e.raw_sketch);
+          sketch_raw(e, R, r0, r + 1, e.sketch.raw_sketch);
           t.stop();
         }
-        const u64 nq = e.raw_sketch.count, m = nq + t_count;
+        const u64 nq = e.sketch.raw_sketch.count, m = nq + t_count;
         if (m >= (1ULL << 32)) throw HipError("[raven_hip] polishing round: a read batch with >= 2^32 minimizers");
-        unsigned char* cv = e.index_sketch.val.get<unsigned char>((m + 1) * vb);
-        u64* co = e.index_sketch.org.get<u64>(m + 1);
+        unsigned char* cv = e.sketch.index_sketch.val.get<unsigned char>((m + 1) * vb);
+        u64* co = e.sketch.index_sketch.org.get<u64>(m + 1);
         if (nq) {
-          RVN_HIP(hipMemcpyAsync(cv, e.raw_sketch.val.ptr, nq * vb, hipMemcpyDeviceToDevice, s));
-          RVN_KLAUNCH(kKGather, flag_origins_kernel<<<div_up(nq, 256), 256, 0, s>>>(e.raw_sketch.org.as<u64>(), nq,
+          RVN_HIP(hipMemcpyAsync(cv, e.sketch.raw_sketch.val.ptr, nq * vb, hipMemcpyDeviceToDevice, s));
+          RVN_KLAUNCH(kKGather, flag_origins_kernel<<<div_up(nq, 256), 256, 0, s>>>(e.sketch.raw_sketch.org.as<u64>(), nq,
                                                                                     kQueryFlag | kForeignFlag, co));
         }
-        RVN_HIP(hipMemcpyAsync(cv + nq * vb, e.pl_tval.ptr, t_count * vb, hipMemcpyDeviceToDevice, s));
-        RVN_HIP(hipMemcpyAsync(co + nq, e.pl_torg.ptr, t_count * 8, hipMemcpyDeviceToDevice, s));
-        e.index_sketch.first = r0;
-        e.index_sketch.last = r + 1;
-        e.index_sketch.count = m;
-        index_build(e, e.index_sketch, false);   // stable sort: the reads' entries stay ahead of the targets' in every run
-        e.index.occurrence = occurrence;
-        e.index.has_query_flags = true;
-        e.index.all_query = false;
+        RVN_HIP(hipMemcpyAsync(cv + nq * vb, e.polish.tval.ptr, t_count * vb, hipMemcpyDeviceToDevice, s));
+        RVN_HIP(hipMemcpyAsync(co + nq, e.polish.torg.ptr, t_count * 8, hipMemcpyDeviceToDevice, s));
+        e.sketch.index_sketch.first = r0;
+        e.sketch.index_sketch.last = r + 1;
+        e.sketch.index_sketch.count = m;
+        index_build(e, e.sketch.index_sketch, false);   // stable sort: the reads' entries stay ahead of the targets' in every run
+        e.sketch.index.occurrence = occurrence;
+        e.sketch.index.has_query_flags = true;
+        e.sketch.index.all_query = false;
         map_batch_query_only(e, R, r0, r + 1, nq, mo);
       } else {
         // The reads' sketch does not change between rounds (only the targets do): kept in HBM per read batch and handed to
         // map_batch as its prepared query sketch (round 6: 32 ms of sketch kernels per C4 round).  One read set at a time,
         // within the option's budget; handed back with the scratch (engine_release_scratch).
-        Engine::PolishSketch* slot = nullptr;
+        PolishState::KeptSketch* slot = nullptr;
         const u64 budget = e.opt.polish_sketch_cache_mb < 0 ? cache_default : static_cast<u64>(e.opt.polish_sketch_cache_mb) << 20;
         if (budget) {
-          if (e.polish_sketch_owner != R.serial) {
-            e.polish_sketches.clear();
-            e.polish_sketch_owner = R.serial;
+          if (e.polish.sketch_owner != R.serial) {
+            e.polish.sketches.clear();
+            e.polish.sketch_owner = R.serial;
           }
-          for (auto& c : e.polish_sketches)
+          for (auto& c : e.polish.sketches)
             if (c->first == r0 && c->last == r + 1) slot = c.get();
         }
         if (slot) {  // the kept sketch becomes the query sketch of this call ...
-          swap_sketch(e.query_sketch, slot->sk);
-          e.query_ready = true;
-          e.query_ready_first = r0;
-          e.query_ready_last = r + 1;
-          e.query_ready_minhash = false;
+          swap_sketch(e.sketch.query_sketch, slot->sk);
+          e.sketch.query_ready = {true, r0, r + 1, false};
         }
         map_batch(e, R, r0, r + 1, false, false, false, false, mo);
         if (!slot && budget) {
           u64 held = 0;
-          for (auto& c : e.polish_sketches) held += c->sk.val.cap + c->sk.org.cap + c->sk.read_off.cap;
-          if (held + e.query_sketch.val.cap + e.query_sketch.org.cap + e.query_sketch.read_off.cap <= budget) {
-            e.polish_sketches.emplace_back(new Engine::PolishSketch());
-            slot = e.polish_sketches.back().get();
+          for (auto& c : e.polish.sketches) held += c->sk.val.cap + c->sk.org.cap + c->sk.read_off.cap;
+          if (held + e.sketch.query_sketch.val.cap + e.sketch.query_sketch.org.cap + e.sketch.query_sketch.read_off.cap <= budget) {
+            e.polish.sketches.emplace_back(new PolishState::KeptSketch());
+            slot = e.polish.sketches.back().get();
             slot->first = r0;
             slot->last = r + 1;
           }
         }
-        if (slot) swap_sketch(e.query_sketch, slot->sk);  // ... and goes back (or: the one just computed is kept)
+        if (slot) swap_sketch(e.sketch.query_sketch, slot->sk);  // ... and goes back (or: the one just computed is kept)
       }
       if (n_overlaps) *n_overlaps += mo.n_overlaps;
       const u32 nr = r + 1 - r0;
       RVN_KLAUNCH(kKBestOverlap, best_overlap_kernel<<<div_up(nr, 256), 256, 0, s>>>(
                                      mo.ovl.as<Overlap>(), mo.ovl_read_off.as<u32>(), r0, nr, err_thr,
-                                     e.pl_idmap.as<u32>(), max_id + 1, d_best, d_best_t));
+                                     e.polish.idmap.as<u32>(), max_id + 1, d_best, d_best_t));
       r0 = r + 1;
     }
   } catch (...) {
-    e.keep_anchors = keep;
-    e.polish_sketches.clear();  // (a kept sketch may be out on loan as the query sketch: nothing kept is trusted after a failure)
-    e.polish_sketch_owner = 0;
+    e.map.keep_anchors = keep;
+    e.polish.sketches.clear();  // (a kept sketch may be out on loan as the query sketch: nothing kept is trusted after a failure)
+    e.polish.sketch_owner = 0;
     throw;
   }
-  e.keep_anchors = keep;
+  e.map.keep_anchors = keep;
   RVN_HIP(hipMemcpyAsync(best.data(), d_best + r_first, static_cast<size_t>(nr_all) * sizeof(Overlap), hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(best_t.data(), d_best_t + r_first, static_cast<size_t>(nr_all) * 4, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
@@ -426,7 +423,7 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   polished.assign(T.n, {});
   ratio.assign(T.n, 0.0);
   stats = PolishStats();
-  e.polish_target_reads.assign(T.n, 0);
+  e.polish.target_reads.assign(T.n, 0);
   if (win_count) win_count->assign(T.n, 0);
   if (win_polished) win_polished->assign(T.n, 0);
   if (T.n == 0) return;
@@ -435,12 +432,12 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   // ---- 1. map the reads to the targets; best overlap per read (device), unless the caller supplies the table -----------
   std::vector<Overlap> best;
   std::vector<u32> best_t;
-  if (e.polish_given_valid) {  // rvn_polish_set_best: the sharded round maps a slice of the reads per rank
-    if (e.polish_given_best.size() != R.n)
+  if (e.polish.given_valid) {  // rvn_polish_set_best: the sharded round maps a slice of the reads per rank
+    if (e.polish.given_best.size() != R.n)
       throw std::invalid_argument("[raven_hip] polishing round: the supplied best-overlap table does not match the read set");
-    best.swap(e.polish_given_best);
-    best_t.swap(e.polish_given_best_t);
-    e.polish_given_valid = false;
+    best.swap(e.polish.given_best);
+    best_t.swap(e.polish.given_best_t);
+    e.polish.given_valid = false;
     for (u32 r = 0; r < R.n; ++r)
       if (best_t[r] != 0xFFFFFFFFu && best_t[r] >= T.n)
         throw std::invalid_argument("[raven_hip] polishing round: best-overlap table names a target that does not exist");
@@ -481,7 +478,7 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
     for (u32 r = 0; r < R.n; ++r) {
       if (best_t[r] != 0xFFFFFFFFu) {
         ++stats.n_reads_used;
-        ++e.polish_target_reads[best_t[r]];
+        ++e.polish.target_reads[best_t[r]];
       }
       rec_off[r + 1] = rec_off[r] + wins_of[r];
       job_of[r + 1] = job_of[r] + (wins_of[r] ? 1u : 0u);
@@ -538,19 +535,19 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
       stats.total_ms = ms_since(t_all);
       return;
     }
-    WinMeta* d_meta = e.pl_win_meta.get<WinMeta>(nw + 1);
-    u64* d_fw = e.pl_first_window.get<u64>(first_window.size());
+    WinMeta* d_meta = e.polish.win_meta.get<WinMeta>(nw + 1);
+    u64* d_fw = e.polish.first_window.get<u64>(first_window.size());
     RVN_HIP(hipMemcpyAsync(d_meta, meta.data(), nw * sizeof(WinMeta), hipMemcpyHostToDevice, s));
     RVN_HIP(hipMemcpyAsync(d_fw, first_window.data(), first_window.size() * 8, hipMemcpyHostToDevice, s));
-    (void)e.pl_out.get<u8>(out_total + 16);
+    (void)e.polish.out.get<u8>(out_total + 16);
   }
-  const WinMeta* d_meta = e.pl_win_meta.as<WinMeta>();
-  const u64* d_fw = e.pl_first_window.as<u64>();
-  u8* d_out = e.pl_out.as<u8>();
+  const WinMeta* d_meta = e.polish.win_meta.as<WinMeta>();
+  const u64* d_fw = e.polish.first_window.as<u64>();
+  u8* d_out = e.polish.out.as<u8>();
   lap("planning");
 
   // ---- 2. alignment paths + breakpoints ------------------------------------------------------------------------------
-  NwWindowRec* d_recs = e.pl_recs.get<NwWindowRec>(n_recs + 1);
+  NwWindowRec* d_recs = e.polish.recs.get<NwWindowRec>(n_recs + 1);
   NwStats nst;
   nw_breakpoints(e, T, R, jobs, w, d_recs, n_recs, nst);
   stats.align_ms = nst.ms;
@@ -570,8 +567,8 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   const u64* d_qual_off = nullptr;
   if (h_quals != nullptr) {  // caller-supplied per-base qualities: to HBM for this call
     const u64 qtotal = h_qual_off[R.n];
-    u8* d_q = e.polish_quals.get<u8>(qtotal + 16);
-    u64* d_qo = e.pl_qual_off.get<u64>(static_cast<size_t>(R.n) + 1);
+    u8* d_q = e.polish.quals.get<u8>(qtotal + 16);
+    u64* d_qo = e.polish.qual_off.get<u64>(static_cast<size_t>(R.n) + 1);
     RVN_HIP(hipMemcpyAsync(d_q, h_quals, qtotal, hipMemcpyHostToDevice, s));
     RVN_HIP(hipMemcpyAsync(d_qo, h_qual_off, (static_cast<size_t>(R.n) + 1) * 8, hipMemcpyHostToDevice, s));
     src.read_quals = d_q;
@@ -582,27 +579,29 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
     d_qual_off = R.qual_off.as<u64>();
   }
   const bool any_q = src.read_quals != nullptr;
-  NwJob* d_jobs = e.nw_jobs.get<NwJob>(nj + 1);
+  NwJob* d_jobs = e.nw.jobs.get<NwJob>(nj + 1);
   if (nj) RVN_HIP(hipMemcpyAsync(d_jobs, jobs.data(), static_cast<size_t>(nj) * sizeof(NwJob), hipMemcpyHostToDevice, s));
-  u32* d_win_cnt = e.pl_win_cnt.get<u32>(nw + 1);
-  u32* d_win_fill = e.pl_win_fill.get<u32>(nw + 1);
-  u32* d_win_off = e.pl_win_off.get<u32>(nw + 2);
-  u8* d_keep = e.pl_keep.get<u8>(n_recs + 1);
-  u32* d_misc = e.pl_misc.get<u32>(4);
+  u32* d_win_cnt = e.polish.win_cnt.get<u32>(nw + 1);
+  u32* d_win_fill = e.polish.win_fill.get<u32>(nw + 1);
+  u32* d_win_off = e.polish.win_off.get<u32>(nw + 2);
+  u8* d_keep = e.polish.keep.get<u8>(n_recs + 1);
+  u32* d_misc = e.polish.misc.get<u32>(4);
   RVN_HIP(hipMemsetAsync(d_win_cnt, 0, static_cast<size_t>(nw) * 4, s));
   RVN_HIP(hipMemsetAsync(d_win_fill, 0, static_cast<size_t>(nw) * 4, s));
   RVN_HIP(hipMemsetAsync(d_misc, 0, 16, s));
   if (nj)
     RVN_KLAUNCH(kKLayerBuild, layer_count_kernel<<<div_up(nj, 128), 128, 0, s>>>(d_jobs, nj, d_recs, d_fw, w, W0, W1,
                                                                                  d_win_cnt, d_keep));
-  exclusive_scan_u32_u32(d_win_cnt, d_win_off, nw, e.scan_tmp, s);
+  exclusive_scan_u32_u32(d_win_cnt, d_win_off, nw, e.scratch.scan_tmp, s);
   const u64 n_read_layers = read_back(e, d_win_off + nw, 4);
   const u64 n_lay = n_read_layers + nw;
   if (n_lay >= 0xFFFFFFFFULL) throw std::invalid_argument("[raven_hip] polishing round: too many layers for one batch");
-  PoaLayer* d_lays_tmp = e.pl_lays_tmp.get<PoaLayer>(n_lay + 1);
-  PoaLayer* d_lays = e.pl_lays.get<PoaLayer>(n_lay + 1);
-  u64* d_keys = e.pl_keys.get<u64>(n_lay + 1);
-  PoaWindow* d_wins = e.pl_wins.get<PoaWindow>(nw + 1);
+  e.polish.last_layers.windows = 0;  // (the tables of the round before are overwritten from here on: no record of them)
+  e.polish.last_layers.layers = 0;
+  PoaLayer* d_lays_tmp = e.polish.lays_tmp.get<PoaLayer>(n_lay + 1);
+  PoaLayer* d_lays = e.polish.lays.get<PoaLayer>(n_lay + 1);
+  u64* d_keys = e.polish.keys.get<u64>(n_lay + 1);
+  PoaWindow* d_wins = e.polish.wins.get<PoaWindow>(nw + 1);
   if (nj)
     RVN_KLAUNCH(kKLayerBuild, layer_fill_kernel<<<div_up(nj, 128), 128, 0, s>>>(
                                   d_jobs, nj, d_recs, d_keep, d_fw, w, W0, d_win_off, d_win_fill, d_meta, d_qual_off,
@@ -611,7 +610,7 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
                                                                               d_lays_tmp, d_keys, d_lays, d_wins));
   const u32 max_len = static_cast<u32>(read_back(e, d_misc, 4));
   if (any_q) {  // racon's mean-quality filter as per-layer flags
-    u8* d_ok = e.pl_ok.get<u8>(n_lay + 16);
+    u8* d_ok = e.polish.ok.get<u8>(n_lay + 16);
     layer_quality_kernel<<<div_up(n_lay, 4), 256, 0, s>>>(d_lays, static_cast<u32>(n_lay), src.read_quals, src.qual_shift,
                                                            q_thr, d_ok);
     RVN_LAUNCH_CHECK();
@@ -628,16 +627,16 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   } else {
     stats.n_layers = n_read_layers;
   }
-  e.polish_last_windows = nw;
-  e.polish_last_layers = n_lay;
-  e.polish_last_w0 = W0;
-  e.polish_last_has_ok = any_q;
-  e.polish_last_read_off = R.h_word_off;
+  e.polish.last_layers.w0 = W0;
+  e.polish.last_layers.has_ok = any_q;
+  e.polish.last_layers.read_off = R.h_word_off;  // (assigned, not replaced: 2.4 MB at C4 whose pages stay mapped)
+  e.polish.last_layers.windows = nw;
+  e.polish.last_layers.layers = n_lay;
   lap("window layers");
 
   // ---- 4. window consensus -----------------------------------------------------------------------------------------------
-  u32* d_len = e.pl_len.get<u32>(nw + 1);
-  u32* d_status = e.pl_status.get<u32>(nw + 1);
+  u32* d_len = e.polish.len.get<u32>(nw + 1);
+  u32* d_status = e.polish.status.get<u32>(nw + 1);
   RVN_HIP(hipMemsetAsync(d_len, 0, static_cast<size_t>(nw) * 4, s));
   std::vector<u32> h_status;
   double poa_ms = 0;
@@ -652,13 +651,14 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   lap("POA");
 
   // ---- 5. stitch the windows in order; per-target results -----------------------------------------------------------
-  u64* d_cons_off = e.pl_cons_off.get<u64>(nw + 2);
-  exclusive_scan_u32_u64(d_len, d_cons_off, nw, e.scan_tmp, s);
+  u64* d_cons_off = e.polish.cons_off.get<u64>(nw + 2);
+  exclusive_scan_u32_u64(d_len, d_cons_off, nw, e.scratch.scan_tmp, s);
   std::vector<u64> cons_off(nw + 1);
   RVN_HIP(hipMemcpyAsync(cons_off.data(), d_cons_off, (static_cast<size_t>(nw) + 1) * 8, hipMemcpyDeviceToHost, s));
   RVN_HIP(rvn_stream_sync(s));
   const u64 total = cons_off[nw];
-  u8* d_final = e.pl_final.get<u8>(total + 16);
+  e.polish.last_cons.valid = false;  // (the consensus of the round before is overwritten from here on)
+  u8* d_final = e.polish.stitched.get<u8>(total + 16);
   RVN_KLAUNCH(kKStitch, stitch_kernel<<<nw, 256, 0, s>>>(d_wins, d_len, d_cons_off, d_out, d_final));
   u8* h_final = e.pin_out.get<u8>(total + 16);
   RVN_HIP(hipMemcpyAsync(h_final, d_final, total, hipMemcpyDeviceToHost, s));
@@ -700,17 +700,16 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
       }
     });
     if (too_small) throw std::invalid_argument("[raven_hip] polishing round: output buffer too small");
-    // (a round over every window leaves the targets' consensus, in target order, in pl_final: rvn_polish_output_as_reads)
-    e.pl_last_valid = false;
+    // (a round over every window leaves the targets' consensus, in target order, in `stitched`: rvn_polish_output_as_reads)
     if (W0 == 0 && W1 == n_windows_all && T.n > 0) {
-      e.pl_last_off.assign(static_cast<size_t>(T.n) + 1, 0);
+      e.polish.last_cons.off.assign(static_cast<size_t>(T.n) + 1, 0);
       bool all = true;
       for (u32 t = 0; t < T.n; ++t) {
         all = all && span[t].second > span[t].first;  // (a target without a window in the range has no consensus here)
-        e.pl_last_off[t] = all ? cons_off[span[t].first] : 0;
+        e.polish.last_cons.off[t] = all ? cons_off[span[t].first] : 0;
       }
-      e.pl_last_off[T.n] = total;
-      e.pl_last_valid = all && T.n > 0;
+      e.polish.last_cons.off[T.n] = total;
+      e.polish.last_cons.valid = all && T.n > 0;
     }
     for (u32 t = 0; t < T.n; ++t) {
       ratio[t] = t_windows[t] ? static_cast<double>(t_polished[t]) / t_windows[t] : 0.0;

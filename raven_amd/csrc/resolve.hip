@@ -318,7 +318,7 @@ void phase_chimeric(Engine& e, ResolveState& st, Scratch& S) {
   u32* d_slot = S.slot.get<u32>(static_cast<size_t>(n) + 2);
   chimeric_work_kernel<<<div_up(n, 256), 256, 0, s>>>(st.invalid.as<u8>(), st.rcount.as<u32>(), st.begin.as<u32>(), st.end.as<u32>(), n, d_flag);
   RVN_LAUNCH_CHECK();
-  exclusive_scan_u8_u32(d_flag, d_slot, n, e.scan_tmp, s);
+  exclusive_scan_u8_u32(d_flag, d_slot, n, e.scratch.scan_tmp, s);
   e.h_pin[0] = e.h_pin[1] = 0;
   RVN_HIP(hipMemcpyAsync(e.h_pin, d_gmed, 8, hipMemcpyDeviceToHost, s));
   RVN_HIP(hipMemcpyAsync(e.h_pin + 1, d_slot + n, 4, hipMemcpyDeviceToHost, s));

@@ -123,13 +123,13 @@ void multi_split(Engine& e, Key key, const u64* const* src_cols, u64* const* dst
   if (nb > kSplitMaxBuckets) throw std::invalid_argument("[raven_hip] sharded pass: at most 16 ranks");
   const u32 n_blocks = div_up(n, kSplitTile);
   const size_t cells = static_cast<size_t>(nb) * n_blocks;
-  u32* d_hist = e.sh_hist.get<u32>(cells + 1);
-  u64* d_off = e.sh_off.get<u64>(cells + 2);
+  u32* d_hist = e.shard.hist.get<u32>(cells + 1);
+  u64* d_off = e.shard.off.get<u64>(cells + 2);
   split_count_kernel<Key><<<n_blocks, kSplitThreads, 0, s>>>(key, n, nb, d_hist, n_blocks);
   RVN_LAUNCH_CHECK();
-  exclusive_scan_u32_u64(d_hist, d_off, cells, e.scan_tmp, s);
+  exclusive_scan_u32_u64(d_hist, d_off, cells, e.scratch.scan_tmp, s);
   // device copies of the column pointer tables
-  const u64** d_src = reinterpret_cast<const u64**>(e.sh_ptrs.get<u64>(2 * NCOL + 2 + kSplitMaxBuckets + 2));
+  const u64** d_src = reinterpret_cast<const u64**>(e.shard.ptrs.get<u64>(2 * NCOL + 2 + kSplitMaxBuckets + 2));
   u64** d_dst = const_cast<u64**>(d_src) + NCOL;
   u64* d_starts = reinterpret_cast<u64*>(const_cast<u64**>(d_src) + 2 * NCOL);
   RVN_HIP(hipMemcpyAsync(d_src, src_cols, NCOL * sizeof(u64*), hipMemcpyHostToDevice, s));
@@ -223,7 +223,7 @@ void shard_split_overlaps(Engine& e, const Overlap* d_ovl, u64 n, const u32* bou
 
 u64 shard_count_flagged(Engine& e, const u64* d_org, u64 n) {
   if (n == 0) return 0;
-  unsigned long long* d = e.sh_ptrs.get<unsigned long long>(64);
+  unsigned long long* d = e.shard.ptrs.get<unsigned long long>(64);
   RVN_HIP(hipMemsetAsync(d, 0, 8, e.stream));
   count_flagged_kernel<<<std::min<u32>(div_up(n, 256), 2048), 256, 0, e.stream>>>(d_org, n, d);
   RVN_LAUNCH_CHECK();
@@ -246,20 +246,20 @@ void shard_regroup(Engine& e, u32 world, const u64* const* d_cnt, const u64* con
     RVN_HIP(hipMemsetAsync(d_seg, 0, 8, s));
     return;
   }
-  const u64** d_tab = reinterpret_cast<const u64**>(e.sh_ptrs.get<u64>(world + 64));
+  const u64** d_tab = reinterpret_cast<const u64**>(e.shard.ptrs.get<u64>(world + 64));
   RVN_HIP(hipMemcpyAsync(d_tab, d_cnt, world * sizeof(u64*), hipMemcpyHostToDevice, s));
-  u32* d_total = e.sh_hist.get<u32>(static_cast<size_t>(n_reads) + 1);
+  u32* d_total = e.shard.hist.get<u32>(static_cast<size_t>(n_reads) + 1);
   sum_counts_kernel<<<div_up(n_reads, 256), 256, 0, s>>>(d_tab, world, n_reads, d_total);
   RVN_LAUNCH_CHECK();
-  exclusive_scan_u32_u64(d_total, d_seg, n_reads, e.scan_tmp, s);
-  u64* d_start = e.sh_off.get<u64>(2 * static_cast<size_t>(n_reads) + 4);
+  exclusive_scan_u32_u64(d_total, d_seg, n_reads, e.scratch.scan_tmp, s);
+  u64* d_start = e.shard.off.get<u64>(2 * static_cast<size_t>(n_reads) + 4);
   u64* d_src_off = d_start + n_reads + 1;
   RVN_HIP(hipMemcpyAsync(d_start, d_seg, static_cast<size_t>(n_reads) * 8, hipMemcpyDeviceToDevice, s));
   for (u32 src = 0; src < world; ++src) {
     if (n_src[src]) {
       narrow_u64_u32_kernel<<<div_up(n_reads, 256), 256, 0, s>>>(d_cnt[src], n_reads, d_total);
       RVN_LAUNCH_CHECK();
-      exclusive_scan_u32_u64(d_total, d_src_off, n_reads, e.scan_tmp, s);
+      exclusive_scan_u32_u64(d_total, d_src_off, n_reads, e.scratch.scan_tmp, s);
       regroup_scatter_kernel<<<div_up(n_src[src], 256), 256, 0, s>>>(d_src_off, d_start, n_reads, n_src[src], d_grp[src],
                                                                       d_pos[src], d_grp_out, d_pos_out);
       RVN_LAUNCH_CHECK();
@@ -272,13 +272,13 @@ void shard_regroup(Engine& e, u32 world, const u64* const* d_cnt, const u64* con
 // d_off[r] = first overlap of lhs read r in a list grouped by ascending lhs id (n_reads + 1 entries)
 void shard_lhs_offsets(Engine& e, const Overlap* d_ovl, u64 n, u32 n_reads, u32* d_off) {
   hipStream_t s = e.stream;
-  u32* d_cnt = e.sh_hist.get<u32>(static_cast<size_t>(n_reads) + 1);
+  u32* d_cnt = e.shard.hist.get<u32>(static_cast<size_t>(n_reads) + 1);
   RVN_HIP(hipMemsetAsync(d_cnt, 0, (static_cast<size_t>(n_reads) + 1) * 4, s));
   if (n) {
     lhs_count_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, n, n_reads, d_cnt);
     RVN_LAUNCH_CHECK();
   }
-  exclusive_scan_u32_u32(d_cnt, d_off, n_reads, e.scan_tmp, s);
+  exclusive_scan_u32_u32(d_cnt, d_off, n_reads, e.scratch.scan_tmp, s);
 }
 
 }  // namespace rvn

@@ -282,8 +282,8 @@ void sketch_raw_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, Sketch& 
     out.org.reserve(16);
     return;
   }
-  u32* tile_cnt = e.tmp_a.get<u32>(nt);
-  u32* tile_off = e.tmp_b.get<u32>(static_cast<size_t>(nt) + 1);
+  u32* tile_cnt = e.scratch.tmp_a.get<u32>(nt);
+  u32* tile_off = e.scratch.tmp_b.get<u32>(static_cast<size_t>(nt) + 1);
   RVN_KLAUNCH(kKSketchCount, sketch_kernel<V, false><<<nt, kThreads, 0, s>>>(
                                  r.packed.as<u64>(), r.word_off.as<u64>(), r.len.as<u32>(), r.id.as<u32>(),
                                  r.tile_read.as<u32>(), r.tile_start.as<u32>(), tf, e.k, e.w, tile_cnt, nullptr,
@@ -297,7 +297,7 @@ void sketch_raw_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, Sketch& 
   if (const char* lim = knob("RVN_SKETCH_LIMIT")) limit = std::strtoull(lim, nullptr, 10);  // (tests: the refusal without 13 Gbases)
 #endif
   if (static_cast<u64>(nt) * kSketchTile >= limit) {
-    unsigned long long* d_sum = e.sketch_sum.get<unsigned long long>(1);
+    unsigned long long* d_sum = e.sketch.sum.get<unsigned long long>(1);
     RVN_HIP(hipMemsetAsync(d_sum, 0, 8, s));
     sum_u32_kernel<<<std::min<u32>(div_up(nt, 1024), 4096), 256, 0, s>>>(tile_cnt, nt, d_sum);
     RVN_LAUNCH_CHECK();
@@ -306,7 +306,7 @@ void sketch_raw_impl(Engine& e, const ReadsDev& r, u32 first, u32 last, Sketch& 
       throw std::invalid_argument("[raven_hip] a sketch of " + std::to_string(sum) + " minimizers in one call (reads " + std::to_string(first) +
                                   " .. " + std::to_string(last) + "): 2^32 or more are not supported — sketch the range in pieces");
   }
-  exclusive_scan_u32_u32(tile_cnt, tile_off, nt, e.scan_tmp, s);
+  exclusive_scan_u32_u32(tile_cnt, tile_off, nt, e.scratch.scan_tmp, s);
   const u32 total = static_cast<u32>(read_back(e, tile_off + nt, 4));
   V* val = out.val.get<V>(static_cast<size_t>(total) + 1);
   u64* org = out.org.get<u64>(static_cast<size_t>(total) + 1);
@@ -338,13 +338,13 @@ void sketch_minhash_impl(Engine& e, const ReadsDev& r, const Sketch& raw, Sketch
   const V* val = raw.val.as<V>();
   const u64* org = raw.org.as<u64>();
   const u32* raw_read_off = raw.read_off.as<u32>();
-  u8* flags = e.tmp_c.get<u8>(static_cast<size_t>(total) + 1);
-  u32* fscan = e.tmp_d.get<u32>(static_cast<size_t>(total) + 1);
+  u8* flags = e.scratch.tmp_c.get<u8>(static_cast<size_t>(total) + 1);
+  u32* fscan = e.scratch.tmp_d.get<u32>(static_cast<size_t>(total) + 1);
   const int nbytes = (2 * e.k + 7) / 8;
   RVN_KLAUNCH(kKMinhashSelect, minhash_select_kernel<V><<<nr, kThreads, 0, s>>>(val, raw_read_off, r.len.as<u32>(),
                                                                                 first, e.k, 8 * (nbytes - 1), flags, nullptr,
                                                                                 nullptr));
-  exclusive_scan_u8_u32(flags, fscan, total, e.scan_tmp, s);
+  exclusive_scan_u8_u32(flags, fscan, total, e.scratch.scan_tmp, s);
   const u32 kept = static_cast<u32>(read_back(e, fscan + total, 4));
   V* oval = out.val.get<V>(static_cast<size_t>(kept) + 1);
   u64* oorg = out.org.get<u64>(static_cast<size_t>(kept) + 1);
@@ -399,8 +399,8 @@ u64 sketch_flag_queries(Engine& e, const ReadsDev& r, Sketch& raw) {
   const u64 total = raw.count;
   if (total == 0) return 0;
   const u32 nr = raw.last - raw.first;
-  u8* flags = e.tmp_c.get<u8>(static_cast<size_t>(total) + 1);
-  unsigned long long* kept = e.tmp_e.get<unsigned long long>(2);
+  u8* flags = e.scratch.tmp_c.get<u8>(static_cast<size_t>(total) + 1);
+  unsigned long long* kept = e.scratch.tmp_e.get<unsigned long long>(2);
   RVN_HIP(hipMemsetAsync(kept, 0, 8, s));
   const int nbytes = (2 * e.k + 7) / 8;
   if (e.val64) {
@@ -420,8 +420,8 @@ void sketch_range(Engine& e, const ReadsDev& r, u32 first, u32 last, bool minhas
     sketch_raw(e, r, first, last, out);
     return;
   }
-  sketch_raw(e, r, first, last, e.raw_sketch);
-  sketch_minhash(e, r, e.raw_sketch, out);
+  sketch_raw(e, r, first, last, e.sketch.raw_sketch);
+  sketch_minhash(e, r, e.sketch.raw_sketch, out);
 }
 
 // ---- packing of one-byte codes (rvn_reads_upload_codes: consensus of a polishing round -> targets of the next) ------

@@ -49,7 +49,7 @@ int radix_sort_pairs_host(Engine& e, uint64_t* keys, uint64_t* values, u64 n, in
     RVN_HIP(hipMemcpy(k0, hk.data(), n * sizeof(K), hipMemcpyHostToDevice));
     RVN_HIP(hipMemcpy(v0, hv.data(), n * sizeof(V), hipMemcpyHostToDevice));
   }
-  const int cur = sort(k0, k1, v0, v1, n, key_bits, e.sort_tmp, e.scan_tmp, e.stream, kKRsUpsweep, kKRsDownsweep, skip);
+  const int cur = sort(k0, k1, v0, v1, n, key_bits, e.scratch.sort_tmp, e.scratch.scan_tmp, e.stream, kKRsUpsweep, kKRsDownsweep, skip);
   RVN_HIP(rvn_stream_sync(e.stream));
   if (n) {
     RVN_HIP(hipMemcpy(hk.data(), cur ? k1 : k0, n * sizeof(K), hipMemcpyDeviceToHost));
@@ -73,7 +73,7 @@ int exclusive_scan_host(Engine& e, const uint64_t* in, uint64_t* out, u64 n, u32
   In* d_in = bi.get<In>(n + in_off + 1) + in_off;
   Out* d_out = bo.get<Out>(n + out_off + 2) + out_off;
   if (n) RVN_HIP(hipMemcpy(d_in, hi.data(), n * sizeof(In), hipMemcpyHostToDevice));
-  scan(d_in, d_out, n, e.scan_tmp, e.stream);
+  scan(d_in, d_out, n, e.scratch.scan_tmp, e.stream);
   RVN_HIP(rvn_stream_sync(e.stream));
   std::vector<Out> ho(n + 1);
   RVN_HIP(hipMemcpy(ho.data(), d_out, (n + 1) * sizeof(Out), hipMemcpyDeviceToHost));
@@ -474,6 +474,14 @@ int rvn_test_exclusive_scan(int variant, const uint64_t* in, uint64_t n, uint32_
     if (variant == 1) return exclusive_scan_host<u32, u32>(e, in, out, n, in_offset_items, out_offset_items, exclusive_scan_u32_u32);
     return exclusive_scan_host<u8, u32>(e, in, out, n, in_offset_items, out_offset_items, exclusive_scan_u8_u32);
   });
+}
+
+int rvn_test_engine_scratch_bytes(rvn_engine* h, uint64_t* bytes) {
+  if (!h || !bytes) return fail(RVN_EINVAL, "[raven_hip] rvn_test_engine_scratch_bytes: NULL argument");
+  std::lock_guard<std::recursive_mutex> lk(h->e.mu);
+  *bytes = 0;
+  h->e.for_each_group([&](auto& group) { group.for_each_buf([&](DevBuf& b) { *bytes += b.cap; }); });
+  return RVN_OK;
 }
 
 int rvn_test_low_complexity(const uint8_t* codes, uint32_t k) { return lc_kmer_passes(codes, k) ? 1 : 0; }

@@ -193,6 +193,7 @@ _TEST_SIGNATURES = {
     "rvn_test_radix_sort_pairs": (_i32, [_i32, _vp, _vp, _u64, _i32, _i32]),
     "rvn_test_exclusive_scan": (_i32, [_i32, _vp, _u64, _u32, _u32, _vp]),
     "rvn_test_compact_overlap_list": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_test_engine_scratch_bytes": (_i32, [_vp, _pu64]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1298,6 +1299,14 @@ def test_compact_overlap_list(overlaps, keep1, keep2=None):
     _test_check(test_lib().rvn_test_compact_overlap_list(_p(o), o.shape[0], _p(k1), _p(k2), _p(out),
                                                          C.byref(n_out), _p(slot)))
     return out[:n_out.value], slot[:m + 1]
+
+
+def test_engine_scratch_bytes(engine) -> int:
+    """Bytes of device scratch the engine holds, i.e. what release_scratch() would hand back
+    (rvn_test_engine_scratch_bytes)."""
+    n = C.c_uint64(0)
+    _test_check(test_lib().rvn_test_engine_scratch_bytes(engine._h, C.byref(n)))
+    return int(n.value)
 
 
 class HookEngine:
