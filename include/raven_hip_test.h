@@ -139,6 +139,16 @@ int rvn_test_compact_overlap_list(const rvn_overlap* in, uint64_t n, const uint8
  * (every buffer the engine's state groups name for release; the read sets and pass handles are not the engine's).  0 right
  * after a release.  It only reads the handle, so h may also be an engine made by libraven_hip.so of the same build. */
 int rvn_test_engine_scratch_bytes(rvn_engine* h, uint64_t* bytes);
+/* best_overlap_kernel (polish.hip: racon's choice of one overlap per read) ON THE DEVICE on a list given by the host, one
+ * launch as a polishing round makes it for a mapped batch of n reads that starts at read `first`.  overlaps[n_overlaps]:
+ * the batch's overlaps, read i's at [read_off[i], read_off[i + 1]) (read_off[n + 1], ascending, read_off[n] <= n_overlaps).
+ * err_thr: a read is unused when 1 - min(span) / max(span) > err_thr, in doubles.  id_to_target[n_ids]: target index of a
+ * target id (0xFFFFFFFF = none); an rhs_id >= n_ids leaves the read unused.  best / best_target: n_rows rows the caller
+ * fills; the kernel writes the rows [first, first + n) (first + n <= n_rows) and the others come back as they went in.
+ * n == 0: no launch.  Engine of its own (device 0).  RVN_EINVAL for a NULL argument or offsets / rows out of range. */
+int rvn_test_best_overlap(const rvn_overlap* overlaps, uint64_t n_overlaps, const uint32_t* read_off, uint32_t first,
+                          uint32_t n, double err_thr, const uint32_t* id_to_target, uint32_t n_ids, rvn_overlap* best,
+                          uint32_t* best_target, uint32_t n_rows);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

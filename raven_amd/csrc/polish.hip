@@ -24,6 +24,10 @@
 
 #include "nwpath.h"
 #include "poa.h"
+#ifdef RVN_TEST_HOOKS
+#include "../../include/raven_hip_test.h"
+#include "abi.h"
+#endif
 
 namespace rvn {
 
@@ -426,6 +430,8 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   e.polish.target_reads.assign(T.n, 0);
   if (win_count) win_count->assign(T.n, 0);
   if (win_polished) win_polished->assign(T.n, 0);
+  e.polish.last_layers.windows = 0;  // rvn_polish_fetch_layers speaks of THIS round from here on, also when it has no window
+  e.polish.last_layers.layers = 0;
   if (T.n == 0) return;
   double host_ms = 0;
 
@@ -433,11 +439,11 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   std::vector<Overlap> best;
   std::vector<u32> best_t;
   if (e.polish.given_valid) {  // rvn_polish_set_best: the sharded round maps a slice of the reads per rank
+    e.polish.given_valid = false;  // consumed by this round, also when the round refuses it: the next one maps by itself
     if (e.polish.given_best.size() != R.n)
       throw std::invalid_argument("[raven_hip] polishing round: the supplied best-overlap table does not match the read set");
     best.swap(e.polish.given_best);
     best_t.swap(e.polish.given_best_t);
-    e.polish.given_valid = false;
     for (u32 r = 0; r < R.n; ++r)
       if (best_t[r] != 0xFFFFFFFFu && best_t[r] >= T.n)
         throw std::invalid_argument("[raven_hip] polishing round: best-overlap table names a target that does not exist");
@@ -724,4 +730,52 @@ void polish_round(Engine& e, ReadsDev& T, ReadsDev& R, const u8* h_quals, const 
   stats.total_ms = ms_since(t_all);
 }
 
+#ifdef RVN_TEST_HOOKS
+// rvn_test_best_overlap (include/raven_hip_test.h): best_overlap_kernel on a list given by the host, launched as
+// polish_map_best launches it.  Every argument the kernel indexes with is checked by the caller below.
+static void test_best_overlap(Engine& e, const Overlap* ovl, u64 n_ovl, const u32* roff, u32 first, u32 n, double err_thr,
+                              const u32* id_to_t, u32 n_ids, Overlap* best, u32* best_t, u32 n_rows) {
+  hipStream_t s = e.stream;
+  DevBuf b_ovl, b_roff, b_map, b_best, b_best_t;
+  const Overlap* d_ovl = upload(b_ovl, ovl, n_ovl, s);
+  const u32* d_roff = upload(b_roff, roff, static_cast<size_t>(n) + 1, s);
+  const u32* d_map = upload(b_map, id_to_t, n_ids, s);
+  Overlap* d_best = upload(b_best, best, n_rows, s);
+  u32* d_best_t = upload(b_best_t, best_t, n_rows, s);
+  if (n)
+    RVN_KLAUNCH(kKBestOverlap, best_overlap_kernel<<<div_up(n, 256), 256, 0, s>>>(d_ovl, d_roff, first, n, err_thr, d_map,
+                                                                                  n_ids, d_best, d_best_t));
+  RVN_HIP(rvn_stream_sync(s));
+  if (n_rows) {
+    RVN_HIP(hipMemcpy(best, d_best, static_cast<size_t>(n_rows) * sizeof(Overlap), hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(best_t, d_best_t, static_cast<size_t>(n_rows) * 4, hipMemcpyDeviceToHost));
+  }
+}
+#endif  // RVN_TEST_HOOKS
+
 }  // namespace rvn
+
+#ifdef RVN_TEST_HOOKS
+extern "C" int rvn_test_best_overlap(const rvn_overlap* overlaps, uint64_t n_overlaps, const uint32_t* read_off,
+                                     uint32_t first, uint32_t n, double err_thr, const uint32_t* id_to_target,
+                                     uint32_t n_ids, rvn_overlap* best, uint32_t* best_target, uint32_t n_rows) {
+  using namespace rvn;
+  static_assert(sizeof(rvn_overlap) == sizeof(Overlap), "overlap layout");
+  if (!read_off || (n_overlaps && !overlaps) || (n_ids && !id_to_target) || (n_rows && (!best || !best_target)))
+    return fail(RVN_EINVAL, "[raven_hip] rvn_test_best_overlap: NULL argument");
+  if (static_cast<u64>(first) + n > n_rows) return fail(RVN_EINVAL, "[raven_hip] rvn_test_best_overlap: rows outside the output arrays");
+  if (read_off[n] > n_overlaps) return fail(RVN_EINVAL, "[raven_hip] rvn_test_best_overlap: offsets beyond the overlap list");
+  for (u32 i = 0; i < n; ++i)
+    if (read_off[i + 1] < read_off[i]) return fail(RVN_EINVAL, "[raven_hip] rvn_test_best_overlap: offsets must ascend");
+  rvn_engine* h = nullptr;  // an engine of its own (device 0) for the stream
+  int r = rvn_engine_create(&h, 15, 5, 500, 4, 100, 10000, 0);
+  if (r != RVN_OK) return r;
+  r = guarded(h, true, "", [&](Engine& e) -> int {
+    test_best_overlap(e, reinterpret_cast<const Overlap*>(overlaps), n_overlaps, read_off, first, n, err_thr, id_to_target,
+                      n_ids, reinterpret_cast<Overlap*>(best), best_target, n_rows);
+    return RVN_OK;
+  });
+  rvn_engine_destroy(h);
+  return r;
+}
+#endif  // RVN_TEST_HOOKS

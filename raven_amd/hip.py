@@ -194,6 +194,7 @@ _TEST_SIGNATURES = {
     "rvn_test_exclusive_scan": (_i32, [_i32, _vp, _u64, _u32, _u32, _vp]),
     "rvn_test_compact_overlap_list": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rvn_test_engine_scratch_bytes": (_i32, [_vp, _pu64]),
+    "rvn_test_best_overlap": (_i32, [_vp, _u64, _vp, _u32, _u32, _dbl, _vp, _u32, _vp, _vp, _u32]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1307,6 +1308,21 @@ def test_engine_scratch_bytes(engine) -> int:
     n = C.c_uint64(0)
     _test_check(test_lib().rvn_test_engine_scratch_bytes(engine._h, C.byref(n)))
     return int(n.value)
+
+
+def test_best_overlap(overlaps, read_off, first, err_thr, id_to_target, best, best_target):
+    """best_overlap_kernel (polish.hip) on a host overlap list (rvn_test_best_overlap): read i of the batch has the
+    overlaps [read_off[i], read_off[i + 1]) and writes row first + i of best / best_target, which the caller has filled.
+    Returns (best, best_target) after the one launch; the arguments are left as they are."""
+    o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)
+    off = np.ascontiguousarray(read_off, dtype=np.uint32)
+    idm = np.ascontiguousarray(id_to_target, dtype=np.uint32)
+    b = np.ascontiguousarray(best, dtype=OVERLAP_DTYPE).copy()
+    bt = np.ascontiguousarray(best_target, dtype=np.uint32).copy()
+    assert off.ndim == 1 and off.shape[0] >= 1 and b.shape == bt.shape and b.ndim == 1
+    _test_check(test_lib().rvn_test_best_overlap(_p(o), o.shape[0], _p(off), int(first), off.shape[0] - 1, float(err_thr),
+                                                 _p(idm), idm.shape[0], _p(b), _p(bt), bt.shape[0]))
+    return b, bt
 
 
 class HookEngine:
