@@ -606,6 +606,52 @@ int rvn_layout_force_directed(rvn_engine* e, uint32_t n_components, const uint32
                               const uint64_t* adj_offsets, const uint32_t* adj, uint32_t n_iterations, double* xy_out,
                               rvn_layout_stats* stats);
 
+/* The assembly graph on the device (facade: include/raven_hip/assembly_graph.hpp): raven's
+ * ConstructAssemblyGraph (RavenLib/src/construct.cc:561-648) as an edge table in HBM, and the marking halves of
+ * RemoveTransitiveEdges (assemble.cc:23-56) and of RemoveLongEdges' loop (assemble.cc:708-721) on it.  RemoveEdges, tips,
+ * bubbles and unitigs stay the caller's.  A graph is immutable once made.
+ * Node 2i / 2i + 1 = the i-th valid pile and its reverse complement; edge 2j / 2j + 1 = the pair made of the j-th overlap
+ * that OverlapFinalize keeps; the pair of an edge is always id ^ 1.
+ *
+ * rvn_construct_assembly_graph: overlaps = overlaps.back() as rvn_resolve_repeat_induced_overlaps leaves it, pile_begin /
+ * pile_end in bases, median = Pile::median(), invalid 0/1.  Per kept overlap: tail = node(lhs), head = node(rhs) + 1 -
+ * strand, length = lhs_begin - rhs_begin, the pair's length = (len(rhs) - rhs_end) - (len(lhs) - lhs_end) on the finalized
+ * coordinates in uint32 arithmetic; score 4 swaps head and tail and negates both lengths.
+ * rvn_graph_from_edges: the same handle from an existing graph (graph.edges flattened): tail == 0xFFFFFFFF marks an empty
+ * slot (graph.edges[i] == nullptr).
+ * rvn_graph_fetch: every output may be NULL.  sequence_to_node[n_piles] (-1: invalid pile), node_pile / node_coverage
+ * [n_nodes], edge_tail / edge_head / edge_length [n_edges], edge_overlap [n_edges / 2] (index of the pair's overlap in the
+ * caller's list), finalized [n_edges / 2] (the overlaps after OverlapFinalize).  A graph made from edges has only the three
+ * edge arrays.
+ * rvn_graph_mark_transitive: for every node v, every out-edge jt and every out-edge kt of head(jt) (out-edges in
+ * ascending edge id), c = the out-edge of v into head(kt) with the largest id; when c exists and length(jt) + length(kt)
+ * (wrapping in 32 bits) is within 12 % of length(c) either way, c and c ^ 1 are marked.  n_marked = marked ids.
+ * rvn_graph_fetch_transitive: the marked ids in the order in which the reference's marked_edges set first receives them
+ * (nodes ascending, jt, kt, c before its pair) - emplacing them in this order reproduces that set's iteration order - and
+ * (tail & ~1, head & ~1) of the odd ids among them in the same order (2 x n_pairs values): what assemble.cc:58-65 feeds
+ * the nodes' `transitive` sets.
+ * rvn_graph_mark_long_edges: one weight per edge slot; marked[n_edges] (may be NULL) = 1 for an edge kt, and its pair,
+ * of a node with two or more out-edges when another out-edge jt of that node has weight(jt) * 2 < weight(kt).
+ * RVN_EINVAL: an id >= n_piles / n_nodes, pile_end < pile_begin, an overlap of type 3 or 4 on an invalid pile (the
+ * reference would index nodes[-1]), an odd n_edges, an edge whose pair slot is empty, a strand other than 0 or 1, a NaN weight, 2^32
+ * edges or more.
+ * Empty inputs give empty tables. */
+typedef struct rvn_graph rvn_graph;
+int rvn_construct_assembly_graph(rvn_engine* e, const rvn_overlap* overlaps, uint64_t n_overlaps, uint32_t n_piles,
+                                 const uint32_t* pile_begin, const uint32_t* pile_end, const uint16_t* median,
+                                 const uint8_t* invalid, rvn_graph** out);
+int rvn_graph_from_edges(rvn_engine* e, uint32_t n_nodes, uint64_t n_edges, const uint32_t* tail, const uint32_t* head,
+                         const uint32_t* length, rvn_graph** out);
+int rvn_graph_info(const rvn_graph* g, uint32_t* n_nodes, uint64_t* n_edges, uint64_t* n_live_edges);
+int rvn_graph_fetch(const rvn_graph* g, int32_t* sequence_to_node, uint32_t* node_pile, uint16_t* node_coverage,
+                    uint32_t* edge_tail, uint32_t* edge_head, uint32_t* edge_length, uint64_t* edge_overlap,
+                    rvn_overlap* finalized);
+int rvn_graph_mark_transitive(rvn_engine* e, rvn_graph* g, uint64_t* n_marked);
+int rvn_graph_fetch_transitive(const rvn_graph* g, uint32_t* marked_in_insertion_order, uint32_t* transitive_pairs,
+                               uint64_t* n_pairs);
+int rvn_graph_mark_long_edges(rvn_engine* e, const rvn_graph* g, const double* weight, uint8_t* marked, uint64_t* n_marked);
+void rvn_graph_destroy(rvn_graph* g);
+
 /* Tuning a deployment may set; -1 restores the built-in default of any option (so does 0, except for poa_rows_min_windows).
  * No option changes an overlap list, a pile or a layer table; poa_rows_min_windows chooses which window-consensus kernel
  * makes the first attempt, and the two agree on 19 998 of 20 000 C4-like windows, not on every one: a

@@ -590,6 +590,42 @@ struct LayoutStats {
 void layout_force_directed(Engine& e, u32 n_components, const u32* h_off, const double* h_xy, const u64* h_adj_off,
                            const u32* h_adj, u32 n_iterations, double* h_xy_out, LayoutStats& st);
 
+// The assembly graph as an edge table in HBM (graph.hip): ConstructAssemblyGraph (RavenLib/src/construct.cc:561-648), the
+// marking of RemoveTransitiveEdges (assemble.cc:23-56) and of RemoveLongEdges' loop (assemble.cc:708-721).  Node 2i / 2i + 1
+// = the i-th valid pile and its reverse complement, edge 2j / 2j + 1 = the pair of the j-th finalized overlap; an edge's
+// pair is always id ^ 1.  The tables are immutable once made; the marks of the last rvn_graph_mark_transitive come on top.
+struct GraphDev {
+  u32 n_piles = 0, n_nodes = 0;
+  u64 n_edges = 0, n_live = 0;  // slots / slots that hold an edge (tail != kNoEdge)
+  bool constructed = false;     // made from overlaps: the node tables and the edge pairs' sources exist
+  DevBuf seq_to_node, node_pile, node_cov;  // i32[n_piles], u32[n_nodes], u16[n_nodes]
+  DevBuf tail, head, length;                // u32[n_edges]
+  DevBuf edge_overlap, finalized;           // u64[n_edges / 2] index in the caller's list, Overlap[n_edges / 2]
+  DevBuf off;                // u32[n_nodes + 1]: the out-edges of node v are [off[v], off[v + 1]) of both orders below
+  DevBuf out_edge;           // u32[n_live] edge ids by (tail, id): the order of the reference's outedges vectors
+  DevBuf hs_head, hs_edge;   // u32[n_live] heads / edge ids by (tail, head, id): the LAST of a run of equal heads is the
+                             // edge `candidate[head]` ends up with (parallel edges: the largest id wins)
+  bool head_order = false;   // hs_head / hs_edge exist (made by the first transitive marking)
+  bool marked = false;
+  std::vector<u32> order;    // the marked ids in the order the reference's marked_edges first receives them
+  std::vector<u32> pairs;    // (tail & ~1, head & ~1) of the odd ids of `order`, in that order
+};
+struct GraphScratch {
+  DevBuf ovl, spare, reg, keep, slot, invalid, median, deg, k32[2], v32[2], k64[2], v64[2], key1, key2, mark, ids, weight, flags, err;
+  void for_each_buf(const BufFn& f) {
+    f(ovl), f(spare), f(reg), f(keep), f(slot), f(invalid), f(median), f(deg), f(k32[0]), f(k32[1]), f(v32[0]), f(v32[1]);
+    f(k64[0]), f(k64[1]), f(v64[0]), f(v64[1]), f(key1), f(key2), f(mark), f(ids), f(weight), f(flags), f(err);
+  }
+  void release() { release_bufs(*this); }
+};
+// h_* are host arrays; pile_begin / pile_end in bases.  Throws std::invalid_argument for an overlap that finalizes on an
+// invalid pile and for more than 2^32 - 2 edges.
+void graph_construct(Engine& e, const Overlap* h_ovl, u64 m, u32 n_piles, const u32* h_begin, const u32* h_end,
+                     const u16* h_median, const u8* h_invalid, GraphDev& g);
+void graph_from_edges(Engine& e, u32 n_nodes, u64 n_edges, const u32* h_tail, const u32* h_head, const u32* h_length, GraphDev& g);
+u64 graph_mark_transitive(Engine& e, GraphDev& g);  // fills g.order / g.pairs, returns order.size()
+u64 graph_mark_long_edges(Engine& e, const GraphDev& g, const double* h_weight, u8* h_marked);
+
 // ---- the engine: parameters, stream, and one state group per stage, each released by its owner's release() ----
 struct Engine {
   EngineOptions opt;
@@ -610,11 +646,12 @@ struct Engine {
   NwState nw;
   PolishState polish;
   IoState io;
+  GraphScratch graph;
   SharedScratch scratch;
   // every group that owns device buffers (what engine_release_scratch releases)
   template <typename F>
   void for_each_group(F&& f) {
-    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(scratch);
+    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(graph), f(scratch);
   }
   int stage_kind = 0;   // the stage entry point running (engine_release_scratch_if_tight)
   u32 oom_mask = 0;     // kinds of stages that ran out of device memory once: they start from released scratch

@@ -146,6 +146,14 @@ _SIGNATURES = {
     "rvn_group_filter_overlaps_by_identity": (_i32, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _dbl]),
     "rvn_overlap_update_and_type": (_i32, [_vp, _u64, _vp, _vp, _vp, _u32, _vp, _vp]),
     "rvn_layout_force_directed": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "rvn_construct_assembly_graph": (_i32, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _pp]),
+    "rvn_graph_from_edges": (_i32, [_vp, _u32, _u64, _vp, _vp, _vp, _pp]),
+    "rvn_graph_info": (_i32, [_vp, _pu32, _pu64, _pu64]),
+    "rvn_graph_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_graph_mark_transitive": (_i32, [_vp, _vp, _pu64]),
+    "rvn_graph_fetch_transitive": (_i32, [_vp, _vp, _vp, _pu64]),
+    "rvn_graph_mark_long_edges": (_i32, [_vp, _vp, _vp, _vp, _pu64]),
+    "rvn_graph_destroy": (None, [_vp]),
     "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
     "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
     "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
@@ -932,6 +940,30 @@ class Engine:
                                                _p(out), _p(st)))
         return out, {"host_tree_iterations": int(st[0]), "max_depth": int(st[1] & 0xFFFFFFFF)}
 
+    def construct_assembly_graph(self, overlaps, pile_begin, pile_end, median, invalid):
+        """raven::ConstructAssemblyGraph as an edge table on the device (rvn_construct_assembly_graph): overlaps.back(),
+        begin / end in bases, median, invalid 0/1.  Returns a Graph."""
+        o = np.ascontiguousarray(overlaps, dtype=OVERLAP_DTYPE)
+        b = np.ascontiguousarray(pile_begin, dtype=np.uint32)
+        en = np.ascontiguousarray(pile_end, dtype=np.uint32)
+        med = np.ascontiguousarray(median, dtype=np.uint16)
+        inv = np.ascontiguousarray(invalid, dtype=np.uint8)
+        n = b.shape[0]
+        assert en.shape[0] == n and med.shape[0] == n and inv.shape[0] == n
+        h = C.c_void_p()
+        _check(lib().rvn_construct_assembly_graph(self._h, _p(o), o.shape[0], n, _p(b), _p(en), _p(med), _p(inv), C.byref(h)))
+        return Graph(self, h, n)
+
+    def graph_from_edges(self, n_nodes, tail, head, length):
+        """A Graph from flattened graph.edges (rvn_graph_from_edges): tail 0xFFFFFFFF = an empty slot."""
+        t = np.ascontiguousarray(tail, dtype=np.uint32)
+        hd = np.ascontiguousarray(head, dtype=np.uint32)
+        ln = np.ascontiguousarray(length, dtype=np.uint32)
+        assert hd.shape[0] == t.shape[0] == ln.shape[0]
+        h = C.c_void_p()
+        _check(lib().rvn_graph_from_edges(self._h, int(n_nodes), t.shape[0], _p(t), _p(hd), _p(ln), C.byref(h)))
+        return Graph(self, h, None)
+
     def release_scratch(self):
         _check(lib().rvn_engine_release_scratch(self._h))
 
@@ -1125,6 +1157,61 @@ class Engine:
 
     def set_timing(self, enabled: bool):
         lib().rvn_engine_set_timing(self._h, int(enabled))
+
+
+class Graph:
+    """An assembly graph's edge table in HBM (rvn_graph): Engine.construct_assembly_graph / Engine.graph_from_edges."""
+
+    def __init__(self, engine, handle, n_piles):
+        self._e, self._h, self.n_piles = engine, handle, n_piles
+        nn, ne, nl = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(lib().rvn_graph_info(self._h, C.byref(nn), C.byref(ne), C.byref(nl)))
+        self.n_nodes, self.n_edges, self.n_live_edges = nn.value, ne.value, nl.value
+
+    def fetch(self):
+        """dict(tail, head, length) of every edge slot; for a constructed graph also sequence_to_node, node_pile,
+        node_coverage, edge_overlap (per edge pair) and finalized (the overlaps after OverlapFinalize, per edge pair)."""
+        E = self.n_edges
+        r = dict(tail=np.zeros(E, np.uint32), head=np.zeros(E, np.uint32), length=np.zeros(E, np.uint32))
+        if self.n_piles is not None:
+            r.update(sequence_to_node=np.zeros(self.n_piles, np.int32), node_pile=np.zeros(self.n_nodes, np.uint32),
+                     node_coverage=np.zeros(self.n_nodes, np.uint16), edge_overlap=np.zeros(E // 2, np.uint64),
+                     finalized=np.zeros(E // 2, OVERLAP_DTYPE))
+        _check(lib().rvn_graph_fetch(self._h, _p(r.get("sequence_to_node")), _p(r.get("node_pile")), _p(r.get("node_coverage")),
+                                     _p(r["tail"]), _p(r["head"]), _p(r["length"]), _p(r.get("edge_overlap")),
+                                     _p(r.get("finalized"))))
+        return r
+
+    def mark_transitive(self):
+        """RemoveTransitiveEdges' marking (rvn_graph_mark_transitive): (marked ids in the reference's insertion order,
+        (k, 2) uint32 transitive pairs of the odd ids in that order)."""
+        n = C.c_uint64()
+        _check(lib().rvn_graph_mark_transitive(self._e._h, self._h, C.byref(n)))
+        order = np.zeros(n.value, np.uint32)
+        pairs = np.zeros((n.value, 2), np.uint32)
+        npairs = C.c_uint64()
+        _check(lib().rvn_graph_fetch_transitive(self._h, _p(order), _p(pairs), C.byref(npairs)))
+        return order, pairs[:npairs.value].copy()
+
+    def mark_long_edges(self, weight):
+        """RemoveLongEdges' marking loop (rvn_graph_mark_long_edges): (flags uint8[n_edges], number of marked ids)."""
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        assert w.shape[0] == self.n_edges
+        flags = np.zeros(self.n_edges, np.uint8)
+        n = C.c_uint64()
+        _check(lib().rvn_graph_mark_long_edges(self._e._h, self._h, _p(w), _p(flags), C.byref(n)))
+        return flags, n.value
+
+    def close(self):
+        if self._h is not None:
+            lib().rvn_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Group:
