@@ -609,7 +609,7 @@ int rvn_layout_force_directed(rvn_engine* e, uint32_t n_components, const uint32
 /* The assembly graph on the device (facade: include/raven_hip/assembly_graph.hpp): raven's
  * ConstructAssemblyGraph (RavenLib/src/construct.cc:561-648) as an edge table in HBM, and the marking halves of
  * RemoveTransitiveEdges (assemble.cc:23-56) and of RemoveLongEdges' loop (assemble.cc:708-721) on it.  RemoveEdges, tips,
- * bubbles and unitigs stay the caller's.  A graph is immutable once made.
+ * bubbles stay the caller's (unitigs: the next block).  A graph is immutable once made.
  * Node 2i / 2i + 1 = the i-th valid pile and its reverse complement; edge 2j / 2j + 1 = the pair made of the j-th overlap
  * that OverlapFinalize keeps; the pair of an edge is always id ^ 1.
  *
@@ -651,6 +651,76 @@ int rvn_graph_fetch_transitive(const rvn_graph* g, uint32_t* marked_in_insertion
                                uint64_t* n_pairs);
 int rvn_graph_mark_long_edges(rvn_engine* e, const rvn_graph* g, const double* weight, uint8_t* marked, uint64_t* n_marked);
 void rvn_graph_destroy(rvn_graph* g);
+
+/* Unitigs on the device (facade: include/raven_hip/unitigs.hpp): raven::CreateUnitigs
+ * (RavenLib/src/common.cc:32-225, with the unitig constructor graph.cc:27-57) on the edge table as it stands after the
+ * host's surgery, and GetUnitigs' selection (common.cc:227-252) as a device read set.  The chains are found by list
+ * ranking, the sequences are a 2-bit gather out of the reads: no base of a unitig passes through the host.
+ *
+ * A TILING holds, per node, a list of segments (read, first base, length, strand) whose concatenation is the node's
+ * sequence; strand 1 = the reverse complement of that stretch of the read.  `read` is the index of the read in the read
+ * set the tiling was made for.
+ * rvn_tiling_from_piles: node u = one segment (node_pile[u], pile_begin, pile_end - pile_begin, u & 1), with node_pile as
+ * rvn_graph_fetch reports it and pile i = read i.
+ * rvn_tiling_from_segments: the lists as the caller states them (CSR: segment_offsets[n_nodes + 1]).
+ * rvn_tiling_fetch: every output may be NULL; node_length[n_nodes] = the nodes' lengths in bases.
+ *
+ * rvn_graph_create_unitigs: count / coverage per node of the graph (Node::count, Node::coverage), epsilon as the
+ * reference's (42 in front of the layout, 0 in SalvagePlasmids and GetUnitigs), min_unitig_size = the reference's global
+ * (9999).  The graph stays as it is; the result holds what the reference's loop collects before its single RemoveEdges:
+ *   new nodes     id first_node + j (first_node = the graph's n_nodes), j in the order of the reference's factory calls:
+ *                 nodes walked in ascending id, a chain and its paired chain created together when the first node of either
+ *                 is met; even j = the unitig (the orientation that holds that node), j + 1 = its reverse-complement unitig.
+ *                 Per new node: begin / end (after the epsilon trim), is_circular, count (summed in uint32), length in
+ *                 bases, coverage ((coverage(begin) + coverage(end)) / 2 of the unitig, for both), is_unitig (count > 5 and
+ *                 length > min_unitig_size), and the members in walk order (CSR member_offsets[n_new_nodes + 1]): begin ..
+ *                 end of a linear chain, from the creating node on round a circular one.  A non-circular chain of fewer than
+ *                 2 epsilon + 2 nodes (or of one node) makes nothing and consumes no id.
+ *   marked        [n_edges] marked_edges as flags: the chain edges from begin to end, the in-edge of begin and the out-edge
+ *                 of end where they exist, and the pairs of all of them.
+ *   new edges     id first_edge + x (first_edge = the graph's n_edges), in factory order; per unitig with begin != end: the
+ *                 in-edge's replacement, its pair, the out-edge's replacement, its pair; lengths as common.cc:136-159 in
+ *                 uint32 arithmetic.
+ *   sequences     per member but the last the first length(out-edge) bases of the member, then the whole of `end`; a
+ *                 circular chain closes on its creating node and appends nothing.  The reverse-complement unitig is built
+ *                 from the pair edges in the same way.  The new nodes' segment lists are APPENDED to the tiling: a later
+ *                 call on the grown graph (rvn_graph_from_edges with n_nodes + n_new_nodes) finds them under their ids.
+ * rvn_unitigs_fetch: every output may be NULL.
+ * rvn_unitigs_as_reads: the new nodes' sequences as a read set like any other (ids 0 .. n - 1): RVN_UNITIGS_SELECTED = the
+ * new nodes GetUnitigs would return (even id and is_unitig, in node order), RVN_UNITIGS_ALL = every new node.  Equal to
+ * rvn_reads_upload_codes of the same sequences word for word.
+ * rvn_tiling_as_reads: the same for any list of nodes of a tiling (nodes of earlier calls that a later one left standing).
+ * RVN_EINVAL: a segment that names an unknown read, runs past its read or has a strand other than 0 or 1, offsets that
+ * decrease, a node of 2^32 bases or more, a node that names an unknown pile; in rvn_graph_create_unitigs (the message names
+ * the offending id) a chain edge longer than its tail's sequence, an edge table that is not pair-symmetric (tail[e ^ 1] !=
+ * head[e] ^ 1 or head[e ^ 1] != tail[e] ^ 1), a unitig of 2^32 bases or more, a tiling with fewer (or more) nodes than the
+ * graph, epsilon above 2^30, more than 2^31 nodes or 2^32 edge slots with the new ones; in the *_as_reads calls a node that
+ * is not in the tiling, a read set other than the tiling's, an unknown selection.  A refused call leaves the tiling as it was.
+ * Empty graphs give empty tables. */
+typedef struct rvn_tiling rvn_tiling;
+typedef struct rvn_unitigs rvn_unitigs;
+enum { RVN_UNITIGS_SELECTED = 0, RVN_UNITIGS_ALL = 1 };
+int rvn_tiling_from_piles(rvn_engine* e, const rvn_reads* reads, uint32_t n_nodes, const uint32_t* node_pile, uint32_t n_piles,
+                          const uint32_t* pile_begin, const uint32_t* pile_end, rvn_tiling** out);
+int rvn_tiling_from_segments(rvn_engine* e, const rvn_reads* reads, uint32_t n_nodes, const uint64_t* segment_offsets,
+                             const uint32_t* segment_read, const uint32_t* segment_begin, const uint32_t* segment_length,
+                             const uint8_t* segment_strand, rvn_tiling** out);
+int rvn_tiling_info(const rvn_tiling* t, uint32_t* n_nodes, uint64_t* n_segments);
+int rvn_tiling_fetch(const rvn_tiling* t, uint64_t* segment_offsets, uint32_t* segment_read, uint32_t* segment_begin,
+                     uint32_t* segment_length, uint8_t* segment_strand, uint32_t* node_length);
+void rvn_tiling_destroy(rvn_tiling* t);
+int rvn_graph_create_unitigs(rvn_engine* e, const rvn_graph* g, rvn_tiling* t, const uint32_t* count, const uint16_t* coverage,
+                             uint32_t epsilon, uint32_t min_unitig_size, rvn_unitigs** out);
+int rvn_unitigs_info(const rvn_unitigs* u, uint32_t* first_node, uint32_t* n_new_nodes, uint64_t* n_members, uint64_t* first_edge,
+                     uint64_t* n_new_edges);
+int rvn_unitigs_fetch(const rvn_unitigs* u, uint32_t* begin, uint32_t* end, uint8_t* is_circular, uint32_t* count, uint32_t* length,
+                      uint16_t* coverage, uint8_t* is_unitig, uint64_t* member_offsets, uint32_t* members, uint8_t* marked,
+                      uint32_t* edge_tail, uint32_t* edge_head, uint32_t* edge_length);
+void rvn_unitigs_destroy(rvn_unitigs* u);
+int rvn_unitigs_as_reads(rvn_engine* e, const rvn_unitigs* u, const rvn_tiling* t, const rvn_reads* reads, int selection,
+                         rvn_reads** out);
+int rvn_tiling_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* reads, const uint32_t* nodes, uint32_t n,
+                        rvn_reads** out);
 
 /* Tuning a deployment may set; -1 restores the built-in default of any option (so does 0, except for poa_rows_min_windows).
  * No option changes an overlap list, a pile or a layer table; poa_rows_min_windows chooses which window-consensus kernel

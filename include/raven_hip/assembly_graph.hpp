@@ -5,7 +5,7 @@
 //
 // What stays on the host, exactly as there: node sequences (InflateData of the valid region, ReverseAndComplement), the
 // factories' calls in the reference's order, the nodes' `transitive` sets, RemoveEdges (the caller's, found through the
-// graph type's namespace), tips, bubbles, unitigs.
+// graph type's namespace), tips, bubbles.  Unitigs: raven_hip/unitigs.hpp.
 //
 // GraphT needs what the reference uses: nodes, edges (vectors of std::unique_ptr, entries may be null), node_factory /
 // edge_factory with NextIndex() and MakeUnique(...); per node id, pair, coverage, outedges, transitive

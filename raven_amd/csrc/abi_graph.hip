@@ -1,5 +1,6 @@
 // abi_graph.hip — C ABI (include/raven_hip.h): the assembly graph on the device (graph.hip): rvn_construct_assembly_graph,
-// rvn_graph_from_edges, the marking of transitive and long edges, and what a graph handle gives back.
+// rvn_graph_from_edges, the marking of transitive and long edges, and what a graph handle gives back; node sequences as
+// tilings, rvn_graph_create_unitigs and unitig sequences as read sets (unitigs.hip).
 #include <cmath>
 #include <cstring>
 
@@ -12,6 +13,13 @@ struct rvn_graph {
   GraphDev g;
   int device = 0;
 };
+struct rvn_tiling {
+  TilingDev t;
+  int device = 0;
+};
+struct rvn_unitigs {
+  UnitigTables u;
+};
 
 namespace {
 
@@ -20,6 +28,17 @@ constexpr u32 kMaxGraphNodes = 1u << 31;  // node ids are int32 in sequence_to_n
 template <typename T>
 void fetch(T* dst, const DevBuf& src, u64 count) {
   if (dst && count) RVN_HIP(hipMemcpy(dst, src.ptr, count * sizeof(T), hipMemcpyDeviceToHost));
+}
+template <typename T>
+void give(T* dst, const std::vector<T>& src) {
+  if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
+}
+
+int nodes_as_reads(Engine& e, const rvn_tiling* t, const rvn_reads* reads, const std::vector<u32>& nodes, rvn_reads** out) {
+  std::unique_ptr<rvn_reads> rr(new rvn_reads());
+  tiling_as_reads(e, t->t, reads->r, nodes.data(), static_cast<u32>(nodes.size()), rr->r);
+  *out = rr.release();
+  return RVN_OK;
 }
 
 }  // namespace
@@ -147,6 +166,125 @@ void rvn_graph_destroy(rvn_graph* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
   delete g;
+}
+
+int rvn_tiling_from_piles(rvn_engine* h, const rvn_reads* reads, uint32_t n_nodes, const uint32_t* node_pile, uint32_t n_piles,
+                          const uint32_t* pile_begin, const uint32_t* pile_end, rvn_tiling** out) {
+  const bool args_ok = h && reads && out && (n_nodes == 0 || (node_pile && pile_begin && pile_end));
+  return guarded(h, args_ok, "[raven_hip] rvn_tiling_from_piles: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (n_nodes > kMaxGraphNodes) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_from_piles: more than 2^31 nodes");
+    std::unique_ptr<rvn_tiling> t(new rvn_tiling());
+    t->device = e.device;
+    tiling_from_piles(e, reads->r, n_nodes, node_pile, n_piles, pile_begin, pile_end, t->t);
+    *out = t.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_tiling_from_segments(rvn_engine* h, const rvn_reads* reads, uint32_t n_nodes, const uint64_t* segment_offsets,
+                             const uint32_t* segment_read, const uint32_t* segment_begin, const uint32_t* segment_length,
+                             const uint8_t* segment_strand, rvn_tiling** out) {
+  const bool have = segment_offsets && (segment_offsets[n_nodes] == 0 || (segment_read && segment_begin && segment_length && segment_strand));
+  const bool args_ok = h && reads && out && segment_offsets && have;
+  return guarded(h, args_ok, "[raven_hip] rvn_tiling_from_segments: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (n_nodes > kMaxGraphNodes) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_from_segments: more than 2^31 nodes");
+    std::unique_ptr<rvn_tiling> t(new rvn_tiling());
+    t->device = e.device;
+    tiling_from_segments(e, reads->r, n_nodes, segment_offsets, segment_read, segment_begin, segment_length, segment_strand, t->t);
+    *out = t.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_tiling_info(const rvn_tiling* t, uint32_t* n_nodes, uint64_t* n_segments) {
+  return guarded([&]() -> int {
+    if (!t) return fail(RVN_EINVAL, "[raven_hip] NULL tiling");
+    if (n_nodes) *n_nodes = t->t.n_nodes;
+    if (n_segments) *n_segments = t->t.n_segs;
+    return RVN_OK;
+  });
+}
+
+int rvn_tiling_fetch(const rvn_tiling* t, uint64_t* segment_offsets, uint32_t* segment_read, uint32_t* segment_begin,
+                     uint32_t* segment_length, uint8_t* segment_strand, uint32_t* node_length) {
+  return guarded([&]() -> int {
+    if (!t) return fail(RVN_EINVAL, "[raven_hip] NULL tiling");
+    RVN_HIP(hipSetDevice(t->device));
+    tiling_fetch(t->t, segment_offsets, segment_read, segment_begin, segment_length, segment_strand, node_length);
+    return RVN_OK;
+  });
+}
+
+void rvn_tiling_destroy(rvn_tiling* t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  delete t;
+}
+
+int rvn_graph_create_unitigs(rvn_engine* h, const rvn_graph* g, rvn_tiling* t, const uint32_t* count, const uint16_t* coverage,
+                             uint32_t epsilon, uint32_t min_unitig_size, rvn_unitigs** out) {
+  const bool args_ok = h && g && t && out && (g->g.n_nodes == 0 || (count && coverage));
+  return guarded(h, args_ok, "[raven_hip] rvn_graph_create_unitigs: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (g->device != e.device || t->device != e.device)
+      return fail(RVN_EINVAL, "[raven_hip] rvn_graph_create_unitigs: the graph or the tiling lives on another device");
+    std::unique_ptr<rvn_unitigs> u(new rvn_unitigs());
+    graph_create_unitigs(e, g->g, t->t, count, coverage, epsilon, min_unitig_size, u->u);
+    *out = u.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_unitigs_info(const rvn_unitigs* u, uint32_t* first_node, uint32_t* n_new_nodes, uint64_t* n_members, uint64_t* first_edge,
+                     uint64_t* n_new_edges) {
+  return guarded([&]() -> int {
+    if (!u) return fail(RVN_EINVAL, "[raven_hip] NULL unitigs");
+    if (first_node) *first_node = u->u.first_node;
+    if (n_new_nodes) *n_new_nodes = static_cast<u32>(u->u.begin.size());
+    if (n_members) *n_members = u->u.members.size();
+    if (first_edge) *first_edge = u->u.first_edge;
+    if (n_new_edges) *n_new_edges = u->u.edge_tail.size();
+    return RVN_OK;
+  });
+}
+
+int rvn_unitigs_fetch(const rvn_unitigs* u, uint32_t* begin, uint32_t* end, uint8_t* is_circular, uint32_t* count, uint32_t* length,
+                      uint16_t* coverage, uint8_t* is_unitig, uint64_t* member_offsets, uint32_t* members, uint8_t* marked,
+                      uint32_t* edge_tail, uint32_t* edge_head, uint32_t* edge_length) {
+  return guarded([&]() -> int {
+    if (!u) return fail(RVN_EINVAL, "[raven_hip] NULL unitigs");
+    const UnitigTables& x = u->u;
+    give(begin, x.begin), give(end, x.end), give(is_circular, x.is_circular), give(count, x.count), give(length, x.length);
+    give(coverage, x.coverage), give(is_unitig, x.is_unitig), give(member_offsets, x.member_off), give(members, x.members);
+    give(marked, x.marked), give(edge_tail, x.edge_tail), give(edge_head, x.edge_head), give(edge_length, x.edge_length);
+    return RVN_OK;
+  });
+}
+
+void rvn_unitigs_destroy(rvn_unitigs* u) { delete u; }
+
+int rvn_unitigs_as_reads(rvn_engine* h, const rvn_unitigs* u, const rvn_tiling* t, const rvn_reads* reads, int selection,
+                         rvn_reads** out) {
+  return guarded(h, h && u && t && reads && out, "[raven_hip] rvn_unitigs_as_reads: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (selection != RVN_UNITIGS_SELECTED && selection != RVN_UNITIGS_ALL)
+      return fail(RVN_EINVAL, "[raven_hip] rvn_unitigs_as_reads: selection is neither RVN_UNITIGS_SELECTED nor RVN_UNITIGS_ALL");
+    if (t->device != e.device) return fail(RVN_EINVAL, "[raven_hip] rvn_unitigs_as_reads: the tiling lives on another device");
+    std::vector<u32> nodes;
+    for (u32 j = 0; j < u->u.begin.size(); ++j)
+      if (selection == RVN_UNITIGS_ALL || (!(j & 1u) && u->u.is_unitig[j])) nodes.push_back(u->u.first_node + j);
+    return nodes_as_reads(e, t, reads, nodes, out);
+  });
+}
+
+int rvn_tiling_as_reads(rvn_engine* h, const rvn_tiling* t, const rvn_reads* reads, const uint32_t* nodes, uint32_t n, rvn_reads** out) {
+  return guarded(h, h && t && reads && out && (n == 0 || nodes), "[raven_hip] rvn_tiling_as_reads: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (t->device != e.device) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_as_reads: the tiling lives on another device");
+    return nodes_as_reads(e, t, reads, std::vector<u32>(nodes, nodes + n), out);
+  });
 }
 
 }  // extern "C"

@@ -6,6 +6,33 @@
 
 using namespace rvn;
 
+// the tables of a read set whose packed words the device made (r.packed holds them, pad words included)
+void rvn::reads_finish_device_set(Engine& e, ReadsDev& r, const std::vector<u64>& woff, const std::vector<u32>& lens, const uint32_t* ids,
+                                  u64 total_bases) {
+  const u32 n = static_cast<u32>(lens.size());
+  r.n = n;
+  r.h_word_off = woff;
+  r.h_len = lens;
+  r.h_id.resize(n);
+  r.ids_are_indices = true;
+  r.total_bases = total_bases;
+  for (u32 i = 0; i < n; ++i) {
+    r.h_id[i] = ids ? ids[i] : i;
+    if (r.h_id[i] != i || i >= kMaxReadId) r.ids_are_indices = false;
+    if (r.h_id[i] >= kMaxReadId) throw std::invalid_argument("[raven_hip] read ids must be below 2^30");  // (bit 62 of an origin word is kForeignFlag: ADVICE r05)
+  }
+  r.n_words = woff[n];
+  u64* d_wo = r.word_off.get<u64>(static_cast<size_t>(n) + 1);
+  RVN_HIP(hipMemcpy(d_wo, r.h_word_off.data(), (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice));
+  u32* d_len = r.len.get<u32>(static_cast<size_t>(n) + 1);
+  u32* d_id = r.id.get<u32>(static_cast<size_t>(n) + 1);
+  if (n) {
+    RVN_HIP(hipMemcpy(d_len, r.h_len.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
+    RVN_HIP(hipMemcpy(d_id, r.h_id.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
+  }
+  reads_build_tiles(e, r);
+}
+
 extern "C" {
 
 int rvn_reads_upload(rvn_engine* h, const uint64_t* packed, uint64_t n_words, const uint64_t* word_offsets,
@@ -78,27 +105,7 @@ int reads_from_device_codes(Engine& e, const u8* d_codes, const std::vector<u64>
   pack_codes_on_device(e, d_codes, d_boff, d_woff, n, n_words, d_packed);
   RVN_HIP(hipMemsetAsync(d_packed + n_words, 0, 16, e.stream));
   RVN_HIP(rvn_stream_sync(e.stream));
-  r.n = n;
-  r.h_word_off = woff;
-  r.h_len = lens;
-  r.h_id.resize(n);
-  r.ids_are_indices = true;
-  r.total_bases = n_codes;
-  for (u32 i = 0; i < n; ++i) {
-    r.h_id[i] = ids ? ids[i] : i;
-    if (r.h_id[i] != i || i >= kMaxReadId) r.ids_are_indices = false;
-    if (r.h_id[i] >= kMaxReadId) return fail(RVN_EINVAL, "[raven_hip] read ids must be below 2^30");  // (bit 62 of an origin word is kForeignFlag: ADVICE r05)
-  }
-  r.n_words = n_words;
-  u64* d_wo = r.word_off.get<u64>(static_cast<size_t>(n) + 1);
-  RVN_HIP(hipMemcpy(d_wo, r.h_word_off.data(), (static_cast<size_t>(n) + 1) * 8, hipMemcpyHostToDevice));
-  u32* d_len = r.len.get<u32>(static_cast<size_t>(n) + 1);
-  u32* d_id = r.id.get<u32>(static_cast<size_t>(n) + 1);
-  if (n) {
-    RVN_HIP(hipMemcpy(d_len, r.h_len.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
-    RVN_HIP(hipMemcpy(d_id, r.h_id.data(), static_cast<size_t>(n) * 4, hipMemcpyHostToDevice));
-  }
-  reads_build_tiles(e, r);
+  reads_finish_device_set(e, r, woff, lens, ids, n_codes);
   *out = rr.release();
   return RVN_OK;
 }

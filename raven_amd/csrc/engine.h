@@ -626,6 +626,60 @@ void graph_from_edges(Engine& e, u32 n_nodes, u64 n_edges, const u32* h_tail, co
 u64 graph_mark_transitive(Engine& e, GraphDev& g);  // fills g.order / g.pairs, returns order.size()
 u64 graph_mark_long_edges(Engine& e, const GraphDev& g, const double* h_weight, u8* h_marked);
 
+// Node sequences as tilings (unitigs.hip; rules: unitig_rules.h): per node a list of read segments whose concatenation is
+// the node's sequence.  A tiling belongs to ONE read set (reads_serial) and only ever grows: raven::CreateUnitigs appends
+// the new nodes' lists, so a later call on the grown graph finds them under their ids.
+struct Segment;  // unitig_rules.h
+struct TilingDev {
+  u32 n_nodes = 0;
+  u64 n_segs = 0;
+  u64 reads_serial = 0;
+  DevBuf seg_off;  // u64[n_nodes + 1]
+  DevBuf seg;      // Segment[n_segs]
+  DevBuf cum;      // u32[n_segs]: bases of the node in front of the segment
+  DevBuf len;      // u32[n_nodes]
+  std::vector<u32> h_len;
+};
+// What raven::CreateUnitigs (RavenLib/src/common.cc:32-225) collects before its single RemoveEdges, as flat host tables:
+// new node j has id first_node + j (even j: a unitig, j + 1: its reverse-complement unitig), new edge x id first_edge + x.
+struct UnitigTables {
+  u32 first_node = 0;
+  u64 first_edge = 0;
+  std::vector<u32> begin, end, count, length;
+  std::vector<u16> coverage;
+  std::vector<u8> is_circular, is_unitig;
+  std::vector<u64> member_off;  // [new nodes + 1]
+  std::vector<u32> members;     // in walk order
+  std::vector<u8> marked;       // [first_edge]: marked_edges as flags
+  std::vector<u32> edge_tail, edge_head, edge_length;
+};
+struct UnitigScratch {
+  DevBuf indeg, outdeg, in_e, out_e, succ, cls, ptr[2], dist[2], endn[2], mn[2], cyc, flag, slot, cbegin, chain_of_end, chain_len;
+  DevBuf count, cov, mcount, moff, members, mnode, mlen, mseg, mcnt, lenscan, segscan, cntscan, mark, err;
+  DevBuf ubegin, uend, ucount, ulen, ucov, ucirc, uis, useg, ecnt, eoff, etail, ehead, elen, nodes, woff;
+  void for_each_buf(const BufFn& f) {
+    f(indeg), f(outdeg), f(in_e), f(out_e), f(succ), f(cls), f(ptr[0]), f(ptr[1]), f(dist[0]), f(dist[1]), f(endn[0]), f(endn[1]);
+    f(mn[0]), f(mn[1]), f(cyc), f(flag), f(slot), f(cbegin), f(chain_of_end), f(chain_len);
+    f(count), f(cov), f(mcount), f(moff), f(members), f(mnode), f(mlen), f(mseg), f(mcnt), f(lenscan), f(segscan), f(cntscan), f(mark), f(err);
+    f(ubegin), f(uend), f(ucount), f(ulen), f(ucov), f(ucirc), f(uis), f(useg), f(ecnt), f(eoff), f(etail), f(ehead), f(elen), f(nodes), f(woff);
+  }
+  void release() { release_bufs(*this); }
+};
+// h_* are host arrays.  Every one of these throws std::invalid_argument for what include/raven_hip.h lists as refused.
+void tiling_from_piles(Engine& e, const ReadsDev& R, u32 n_nodes, const u32* h_node_pile, u32 n_piles, const u32* h_begin,
+                       const u32* h_end, TilingDev& T);
+void tiling_from_segments(Engine& e, const ReadsDev& R, u32 n_nodes, const u64* h_seg_off, const u32* h_read, const u32* h_begin,
+                          const u32* h_length, const u8* h_strand, TilingDev& T);
+void tiling_fetch(const TilingDev& T, u64* seg_off, u32* read, u32* begin, u32* length, u8* strand, u32* node_length);
+// the grown tiling and the tables; nothing of T changes when the call throws
+void graph_create_unitigs(Engine& e, const GraphDev& g, TilingDev& T, const u32* h_count, const u16* h_coverage, u32 epsilon,
+                          u32 min_unitig_size, UnitigTables& out);
+// the sequences of the listed nodes of T as a read set over the reads R the tiling was made for (read i = node h_nodes[i])
+void tiling_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, const u32* h_nodes, u32 n, ReadsDev& out);
+// what every device-made read set shares once its packed words lie in r.packed (abi_reads.hip): the tables, the ids, the tiles
+void reads_finish_device_set(Engine& e, ReadsDev& r, const std::vector<u64>& woff, const std::vector<u32>& lens, const uint32_t* ids,
+                             u64 total_bases);
+
 // ---- the engine: parameters, stream, and one state group per stage, each released by its owner's release() ----
 struct Engine {
   EngineOptions opt;
@@ -647,11 +701,12 @@ struct Engine {
   PolishState polish;
   IoState io;
   GraphScratch graph;
+  UnitigScratch unitig;
   SharedScratch scratch;
   // every group that owns device buffers (what engine_release_scratch releases)
   template <typename F>
   void for_each_group(F&& f) {
-    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(graph), f(scratch);
+    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(graph), f(unitig), f(scratch);
   }
   int stage_kind = 0;   // the stage entry point running (engine_release_scratch_if_tight)
   u32 oom_mask = 0;     // kinds of stages that ran out of device memory once: they start from released scratch

@@ -154,6 +154,17 @@ _SIGNATURES = {
     "rvn_graph_fetch_transitive": (_i32, [_vp, _vp, _vp, _pu64]),
     "rvn_graph_mark_long_edges": (_i32, [_vp, _vp, _vp, _vp, _pu64]),
     "rvn_graph_destroy": (None, [_vp]),
+    "rvn_tiling_from_piles": (_i32, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _pp]),
+    "rvn_tiling_from_segments": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _pp]),
+    "rvn_tiling_info": (_i32, [_vp, _pu32, _pu64]),
+    "rvn_tiling_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_tiling_destroy": (None, [_vp]),
+    "rvn_graph_create_unitigs": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _pp]),
+    "rvn_unitigs_info": (_i32, [_vp, _pu32, _pu32, _pu64, _pu64, _pu64]),
+    "rvn_unitigs_fetch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rvn_unitigs_destroy": (None, [_vp]),
+    "rvn_unitigs_as_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _pp]),
+    "rvn_tiling_as_reads": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp]),
     "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
     "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
     "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
@@ -964,6 +975,30 @@ class Engine:
         _check(lib().rvn_graph_from_edges(self._h, int(n_nodes), t.shape[0], _p(t), _p(hd), _p(ln), C.byref(h)))
         return Graph(self, h, None)
 
+    def tiling_from_piles(self, reads: Reads, node_pile, pile_begin, pile_end):
+        """Node sequences as read segments (rvn_tiling_from_piles): node u = pile node_pile[u]'s valid region, reverse
+        complemented for odd u; node_pile as Graph.fetch() reports it, begin / end in bases.  Returns a Tiling."""
+        npile = np.ascontiguousarray(node_pile, dtype=np.uint32)
+        b = np.ascontiguousarray(pile_begin, dtype=np.uint32)
+        en = np.ascontiguousarray(pile_end, dtype=np.uint32)
+        assert b.shape[0] == en.shape[0]
+        h = C.c_void_p()
+        _check(lib().rvn_tiling_from_piles(self._h, reads._h, npile.shape[0], _p(npile), b.shape[0], _p(b), _p(en), C.byref(h)))
+        return Tiling(self, reads, h)
+
+    def tiling_from_segments(self, reads: Reads, offsets, read, begin, length, strand):
+        """A Tiling from caller-stated segment lists (rvn_tiling_from_segments): CSR offsets[n_nodes + 1] over (read index,
+        first base, length, strand) arrays."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        r = np.ascontiguousarray(read, dtype=np.uint32)
+        b = np.ascontiguousarray(begin, dtype=np.uint32)
+        ln = np.ascontiguousarray(length, dtype=np.uint32)
+        st = np.ascontiguousarray(strand, dtype=np.uint8)
+        assert r.shape[0] == b.shape[0] == ln.shape[0] == st.shape[0] and off.shape[0] >= 1
+        h = C.c_void_p()
+        _check(lib().rvn_tiling_from_segments(self._h, reads._h, off.shape[0] - 1, _p(off), _p(r), _p(b), _p(ln), _p(st), C.byref(h)))
+        return Tiling(self, reads, h)
+
     def release_scratch(self):
         _check(lib().rvn_engine_release_scratch(self._h))
 
@@ -1202,9 +1237,116 @@ class Graph:
         _check(lib().rvn_graph_mark_long_edges(self._e._h, self._h, _p(w), _p(flags), C.byref(n)))
         return flags, n.value
 
+    def create_unitigs(self, tiling, count, coverage, epsilon=0, min_unitig_size=9999):
+        """raven::CreateUnitigs on the edge table (rvn_graph_create_unitigs): count / coverage per node.  The tiling grows
+        by the new nodes; returns a Unitigs."""
+        c = np.ascontiguousarray(count, dtype=np.uint32)
+        cov = np.ascontiguousarray(coverage, dtype=np.uint16)
+        assert c.shape[0] == self.n_nodes and cov.shape[0] == self.n_nodes
+        h = C.c_void_p()
+        _check(lib().rvn_graph_create_unitigs(self._e._h, self._h, tiling._h, _p(c), _p(cov), int(epsilon), int(min_unitig_size),
+                                              C.byref(h)))
+        return Unitigs(self._e, tiling, h)
+
     def close(self):
         if self._h is not None:
             lib().rvn_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Tiling:
+    """Node sequences as lists of read segments in HBM (rvn_tiling): Engine.tiling_from_piles / tiling_from_segments.
+    Graph.create_unitigs appends the new nodes' lists."""
+
+    def __init__(self, engine, reads, handle):
+        self._e, self.reads, self._h = engine, reads, handle
+
+    @property
+    def n_nodes(self):
+        n, m = C.c_uint32(), C.c_uint64()
+        _check(lib().rvn_tiling_info(self._h, C.byref(n), C.byref(m)))
+        return n.value
+
+    def fetch(self):
+        """dict(offsets uint64[n_nodes + 1], read, begin, length uint32[segments], strand uint8[segments], node_length)."""
+        n, m = C.c_uint32(), C.c_uint64()
+        _check(lib().rvn_tiling_info(self._h, C.byref(n), C.byref(m)))
+        r = dict(offsets=np.zeros(n.value + 1, np.uint64), read=np.zeros(m.value, np.uint32), begin=np.zeros(m.value, np.uint32),
+                 length=np.zeros(m.value, np.uint32), strand=np.zeros(m.value, np.uint8), node_length=np.zeros(n.value, np.uint32))
+        _check(lib().rvn_tiling_fetch(self._h, _p(r["offsets"]), _p(r["read"]), _p(r["begin"]), _p(r["length"]), _p(r["strand"]),
+                                      _p(r["node_length"])))
+        return r
+
+    def as_reads(self, nodes) -> Reads:
+        """The sequences of the listed nodes as a read set (rvn_tiling_as_reads)."""
+        ids = np.ascontiguousarray(nodes, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(lib().rvn_tiling_as_reads(self._e._h, self._h, self.reads._h, _p(ids), ids.shape[0], C.byref(h)))
+        return _device_reads(self._e, h)
+
+    def close(self):
+        if self._h is not None:
+            lib().rvn_tiling_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _device_reads(engine, handle) -> Reads:
+    """A Reads over a read set the library made: its lengths come from the handle."""
+    n = C.c_uint32()
+    _check(lib().rvn_reads_info(handle, C.byref(n), None, None, None, None))
+    lens = np.zeros(n.value, np.uint32)
+    _check(lib().rvn_reads_fetch(handle, None, None, _p(lens), None, None))
+    return Reads(engine, CodeSet(lens), handle=handle)
+
+
+UNITIGS_SELECTED, UNITIGS_ALL = 0, 1
+
+
+class Unitigs:
+    """What raven::CreateUnitigs collects before its RemoveEdges, as flat tables (rvn_unitigs): Graph.create_unitigs."""
+
+    def __init__(self, engine, tiling, handle):
+        self._e, self.tiling, self._h = engine, tiling, handle
+        fn, nn, nm, fe, ne = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().rvn_unitigs_info(self._h, C.byref(fn), C.byref(nn), C.byref(nm), C.byref(fe), C.byref(ne)))
+        self.first_node, self.n_new_nodes, self.n_members = fn.value, nn.value, nm.value
+        self.first_edge, self.n_new_edges = fe.value, ne.value
+
+    def fetch(self):
+        """dict(begin, end, is_circular, count, length, coverage, is_unitig per new node; member_offsets, members; marked
+        per edge slot of the graph; edge_tail, edge_head, edge_length per new edge)."""
+        U, E = self.n_new_nodes, self.n_new_edges
+        r = dict(begin=np.zeros(U, np.uint32), end=np.zeros(U, np.uint32), is_circular=np.zeros(U, np.uint8),
+                 count=np.zeros(U, np.uint32), length=np.zeros(U, np.uint32), coverage=np.zeros(U, np.uint16),
+                 is_unitig=np.zeros(U, np.uint8), member_offsets=np.zeros(U + 1, np.uint64),
+                 members=np.zeros(self.n_members, np.uint32), marked=np.zeros(self.first_edge, np.uint8),
+                 edge_tail=np.zeros(E, np.uint32), edge_head=np.zeros(E, np.uint32), edge_length=np.zeros(E, np.uint32))
+        _check(lib().rvn_unitigs_fetch(self._h, *[_p(r[k]) for k in (
+            "begin", "end", "is_circular", "count", "length", "coverage", "is_unitig", "member_offsets", "members", "marked",
+            "edge_tail", "edge_head", "edge_length")]))
+        return r
+
+    def as_reads(self, selection=UNITIGS_SELECTED) -> Reads:
+        """The new nodes' sequences as a read set (rvn_unitigs_as_reads): GetUnitigs' choice, or UNITIGS_ALL."""
+        h = C.c_void_p()
+        _check(lib().rvn_unitigs_as_reads(self._e._h, self._h, self.tiling._h, self.tiling.reads._h, int(selection), C.byref(h)))
+        return _device_reads(self._e, h)
+
+    def close(self):
+        if self._h is not None:
+            lib().rvn_unitigs_destroy(self._h)
             self._h = None
 
     def __del__(self):
