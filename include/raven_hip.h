@@ -435,7 +435,13 @@ int rvn_shard_piles(rvn_engine* e, const uint32_t* lengths, uint32_t n_reads_tot
                     uint64_t n, uint32_t kmax, rvn_pass1** out);
 
 /* piles kept across the flush windows of a pass: create once, merge the Map outputs of every window (each merge =
- * the serial merge + AddLayers + top-kMax truncation of one flush, construct.cc:72-110); rvn_shard_piles = both */
+ * the serial merge + AddLayers + top-kMax truncation of one flush, construct.cc:72-110); rvn_shard_piles = both.
+ * Precondition of every merge entry: the list is grouped by ascending lhs_id, every id is < n_reads_total and every
+ * overlap has lhs_id < rhs_id (Map with avoid_equal and avoid_symmetric) — a pile's list is built as kept ++ reversed
+ * incoming ++ own, which is the reference's order only then.  The host entries (rvn_shard_piles, rvn_shard_piles_merge)
+ * check all three and return RVN_EINVAL, leaving the pass as it was; the _dev entries (rvn_shard_piles_merge_dev,
+ * rvn_shard_piles_merge_parts_dev, rvn_shard_piles_dev) do NOT look at the list: there the caller guarantees them, and
+ * a list that breaks them gives an undefined result. */
 int rvn_shard_piles_create(rvn_engine* e, const uint32_t* lengths, uint32_t n_reads_total, rvn_pass1** out);
 int rvn_shard_piles_merge(rvn_pass1* p, const rvn_overlap* overlaps, uint64_t n, uint32_t kmax);
 int rvn_shard_piles_merge_dev(rvn_pass1* p, const rvn_overlap* d_overlaps, const uint32_t* d_overlap_read_off, uint64_t n,

@@ -398,6 +398,10 @@ int rvn_shard_piles_merge(rvn_pass1* p, const rvn_overlap* overlaps, uint64_t n,
     for (u64 i = 0; i < n; ++i) {
       if (ov[i].lhs_id >= n_reads_total || ov[i].rhs_id >= n_reads_total || ov[i].lhs_id < prev)
         return fail(RVN_EINVAL, "[raven_hip] rvn_shard_piles: overlaps must be ordered by lhs_id and ids < n_reads");
+      // pile_build_kernel puts every reversed overlap of a pile before the pile's own: construct.cc:72-77 only when the
+      // reversed ones come from earlier queries (Map with avoid_equal and avoid_symmetric)
+      if (ov[i].lhs_id >= ov[i].rhs_id)
+        return fail(RVN_EINVAL, "[raven_hip] rvn_shard_piles: every overlap must have lhs_id < rhs_id");
       prev = ov[i].lhs_id;
       ++off[ov[i].lhs_id + 1];
     }
