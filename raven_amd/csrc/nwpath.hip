@@ -29,6 +29,7 @@
 
 #include "engine.h"
 #include "nwpath.h"
+#include "nwplan.h"
 #include "nwsweep.h"
 #include "nwtrace.h"
 #include "wave.h"
@@ -37,26 +38,13 @@ namespace rvn {
 
 namespace {
 
-// kernel variants: (blocks per lane R, lanes per alignment G); narrow rings share a wave (64 / G alignments).  Ordered by
-// the band they hold (G (64 R + 1) - 64 R offsets), i.e. by alignment length.  Several blocks per lane are only used
-// where one block per lane cannot hold the band: variants (2, 8) ... (4, 32) — fewer instructions per block step on
-// paper — were measured and lost (C4 sweep 178 ms with R = 1 wherever possible, 187 ms allowing R = 2, 225 ms allowing
-// R = 4: more registers = fewer waves, a coarser band, costlier ring events).
 constexpr int kNwLaneStripCols = 16;        // columns a walker's strip keeps in LDS (nw_trace_kernel<true>)
 constexpr int kNwGroupLanes = 16;           // lanes per alignment of the group walk (four alignments per wave)
 constexpr u32 kNwGroupWalkMaxJobs = 8192;  // a walk launch of at most this many alignments takes the group walk (two rounds of the
                                            // machine's 4 096 resident groups: beyond that a group's ~3x shorter latency per column loses
                                            // to the lane walk's sixteen times as many alignments in flight — tools/walk_ab.sh)
 constexpr u32 kSideSweepMaxWaves = 2048;    // a sweep launch of at most this many waves goes beside the main stream's (enqueue)
-constexpr u32 kLevels = 8;
-const u32 kRs[kLevels] = {1, 1, 1, 1, 1, 2, 4, 8};
-const u32 kGs[kLevels] = {4, 8, 16, 32, 64, 64, 64, 64};
-// A band no variant's ring holds is swept in stripes (nwpath.h, NwGeo): R = 8, stripes of nw_stripe_lanes super-blocks
-// (default 64, a whole wave), a band of at most kNwMaxStripes such rings (262 144 rows with whole waves, 8 x the widest
-// ring).  Striped jobs are a class of their own, above the variants.
-constexpr u32 kNwMaxStripes = 8;
-constexpr u32 kStriped = kLevels;
-constexpr u32 kClasses = kLevels + 1;
+// (the kernel variants, the striped class above them and everything the host plans with them: nwplan.h)
 
 template <int G>
 __device__ __forceinline__ u32 group_max(u32 v) {
@@ -290,28 +278,9 @@ void launch_sweep(Engine& e, hipStream_t s, const NwJob* d_jobs, const u32* d_id
                                d_status, d_next, stripe)));
 }
 
-// largest threshold whose band fits a ring of G lanes with R blocks each
-u32 kcap_of(u32 n, u32 m, u32 R, u32 G) {
-  const u32 d = n > m ? n - m : m - n;
-  // nw_ring_lanes(lo, hi, R) <= G  <=>  64R + lo + hi <= G (64R + 1);  lo + hi = 2 floor((k - d) / 2) + d
-  const u64 room = static_cast<u64>(G) * (64ULL * R + 1) - 64ULL * R;
-  if (room < d) return 0;
-  const u64 k = d + ((room - d) / 2) * 2 + 1;  // (k - d) / 2 floors: an odd surplus costs nothing
-  return static_cast<u32>(std::min<u64>(k, static_cast<u64>(n) + m));
-}
-
-u32 level_of(const NwJob& J) {
-  if (J.S) return kStriped;
-  for (u32 x = 0; x < kLevels; ++x)
-    if (kRs[x] == J.R && kGs[x] == J.G) return x;
-  return kLevels - 1;
-}
 
 }  // namespace
 
-// Fills the band fields of `jobs` (k, kcap, R, G, hs, ckpt) and produces every job's window records in d_recs
-// (records of a job start at its bp_off; jobs that cannot be aligned keep all-invalid records and are counted).
-//
 // The stage's streams and events, on first use.  HIP multiplexes its streams over a handful of hardware queues (four by
 // default): two walk streams that land on the same queue run one after the other, and the ~100-ms walk of the longest
 // alignments held the walk queued behind it — and with it the sweep waiting for that walk's buffer set
@@ -349,337 +318,227 @@ void NwState::close() {
   drop(side, hipStreamDestroy);
 }
 
-// Schedule: the jobs of a pass go in chunks whose hs + ck fit half the budget, longest jobs first.  The sweeps run on the
-// engine's stream, the walk of chunk i on a second stream beside the sweeps of chunk i + 1 (two buffer sets): a walk is
-// one lane per alignment and latency-bound (~1 us per column), a sweep fills the VALUs — together they cost the time of
-// the sweeps plus the walk of the last, shortest jobs.
+namespace {
+
+using clk = std::chrono::steady_clock;
+double since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+
+// an error in the middle of a pass (a walk that left its band, an allocation that failed) must not leave walks running
+// on the side streams against buffers the next call hands out again
+struct WalkGuard {
+  Engine& e;
+  ~WalkGuard() {
+    if (!std::uncaught_exceptions()) return;
+    for (hipStream_t st2 : e.nw.streams)
+      if (st2) (void)hipStreamSynchronize(st2);
+    for (hipStream_t st2 : e.nw.side)
+      if (st2) (void)hipStreamSynchronize(st2);
+    (void)hipStreamSynchronize(e.stream);
+  }
+};
+
+// hs + ck of the stage's buffer sets: a quarter of the free HBM (at most 64 GB), or engine option nw_budget_mb
+u64 nw_budget(Engine& e) {
+  size_t free_b = 0, total_b = 0;
+  RVN_HIP(hipMemGetInfo(&free_b, &total_b));
+  u64 held = 0;
+  for (const NwState::Set& set : e.nw.sets) held += set.hs.cap + set.ck.cap;
+  u64 budget = std::min<u64>((static_cast<u64>(free_b) + devpool::free_total()) / 4 + held, 64ULL << 30);  // parked blocks count as free
+  if (e.opt.nw_budget_mb > 0) budget = static_cast<u64>(e.opt.nw_budget_mb) << 20;
+  return std::max<u64>(budget, 64ULL << 20);
+}
+
+// One call of nw_breakpoints: what its passes share, and the stream and event protocol that turns a plan (nwplan.h) into
+// launches.  Schedule: the jobs of a pass go in chunks whose hs + ck fit half the budget, longest jobs first.  The sweeps
+// run on the engine's stream, the walk of chunk i on a second stream beside the sweeps of chunk i + 1 (two buffer sets): a
+// walk is one lane per alignment and latency-bound (~1 us per column), a sweep fills the VALUs — together they cost the
+// time of the sweeps plus the walk of the last, shortest jobs.
 //
-// path (the path form, nw_align_paths below): the walks leave their runs instead of window records (d_recs = nullptr,
-// n_recs = 0).  Every pass of walks gets a block of slots of its own, a job's slot there at its bp_off (nw_slot_words of its
-// threshold: known when it is queued); path->slot_end[job] = the device address of the word behind the runs of the job's
-// last walk.  Planning, thresholds, retries, chunks, stripes and the choice of the walk are the same code.
-void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vector<NwJob>& jobs, u32 w,
-                    NwWindowRec* d_recs, u64 n_recs, NwStats& st, std::vector<u32>* distances, NwPathSlots* path) {
-  st = NwStats();
-  const u32 nj = static_cast<u32>(jobs.size());
-  if (distances) distances->assign(nj, ~0u);
-  if (path) path->slot_end.assign(nj, 0);
-  hipStream_t s = e.stream;
-  if (n_recs) RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
-  if (nj == 0) return;
-  RVN_HIP(hipEventRecord(e.ev0, s));
-  if (!e.nw.streams[0]) e.nw.open();
-  // an error in the middle of a pass (a walk that left its band, an allocation that failed) must not leave walks running
-  // on the side streams against buffers the next call hands out again
-  struct WalkGuard {
-    Engine& e;
-    ~WalkGuard() {
-      if (!std::uncaught_exceptions()) return;
-      for (hipStream_t st2 : e.nw.streams)
-        if (st2) (void)hipStreamSynchronize(st2);
-      for (hipStream_t st2 : e.nw.side)
-        if (st2) (void)hipStreamSynchronize(st2);
-      (void)hipStreamSynchronize(e.stream);
-    }
-  } walk_guard{e};
-  double rate = e.nw.rate > 0 ? e.nw.rate : 0.13;  // first call: ONT-like; too small only costs a repeat
-  if (const char* ev = knob("RVN_NW_RATE")) rate = std::atof(ev);  // (debug builds: force repeats)
-  u64 budget = 0;
+// path (the path form, nw_align_paths below): the walks leave their runs instead of window records (d_recs = nullptr).
+// Every pass of walks gets a block of slots of its own, a job's slot there at its bp_off (nw_slot_words of its threshold:
+// known when it is queued); path->slot_end[job] = the device address of the word behind the runs of the job's last walk.
+// Planning, thresholds, retries, chunks, stripes and the choice of the walk are the same code.
+struct NwRun {
+  Engine& e;
+  const ReadsDev& T;
+  const ReadsDev& Rd;
+  std::vector<NwJob>& jobs;
+  const u32 w;
+  NwWindowRec* const d_recs;
+  NwPathSlots* const path;
+  NwStats& st;
+  std::vector<u32>* const distances;
+  const hipStream_t s;
+  const u32 nj;
+  const u64 budget;
   // engine option nw_stripe_lanes: the widest ring of one sweep (variants with wider rings are skipped) = the stripe size
-  const u32 stripe_lanes = e.opt.nw_stripe_lanes > 0 && e.opt.nw_stripe_lanes < 64 ? static_cast<u32>(e.opt.nw_stripe_lanes) : 64u;
-
-  // plan: the narrowest variant whose ring holds the band of k; beyond the widest, stripes (a band of at most kNwMaxStripes
-  // rings whose stored hs + ck fit the budget; otherwise the job is not aligned)
-  auto plan = [&](NwJob& J, u64 k) -> bool {
-    const u32 d = J.n > J.m ? J.n - J.m : J.m - J.n;
-    k = std::max<u64>(std::max<u64>(k, d), 16);
-    k = std::min<u64>(k, static_cast<u64>(J.n) + J.m);  // D(n, m) <= n + m: that threshold never fails
-    J.S = 0;
-    for (u32 lvl = 0; lvl < kLevels; ++lvl) {
-      if (kGs[lvl] > stripe_lanes) continue;
-      const u32 cap = kcap_of(J.n, J.m, kRs[lvl], kGs[lvl]);
-      if (cap >= k) {
-        J.R = kRs[lvl];
-        J.G = kGs[lvl];
-        J.k = static_cast<u32>(k);
-        J.kcap = cap;
-        return true;
-      }
-    }
-    const u32 cap = kcap_of(J.n, J.m, 8, kNwMaxStripes * stripe_lanes);
-    if (cap < k) return false;
-    const NwGeo g = nw_geo_striped(J.n, J.m, static_cast<u32>(k), 8, stripe_lanes);
-    if (g.hs_words() * 4 + g.ck_entries() * 16 > budget) return false;
-    J.R = 8;
-    J.G = 64;
-    J.S = stripe_lanes;
-    J.k = static_cast<u32>(k);
-    J.kcap = cap;
-    return true;
-  };
-  std::vector<u32> valid;
-  for (u32 i = 0; i < nj; ++i) {
-    const NwJob& J = jobs[i];
-    if (J.n == 0 || J.m == 0 || J.n >= (1u << 30) || J.m >= (1u << 30)) ++st.n_unaligned;
-    else valid.push_back(i);
-  }
-
-  {
-    size_t free_b = 0, total_b = 0;
-    RVN_HIP(hipMemGetInfo(&free_b, &total_b));
-    u64 held = 0;
-    for (const NwState::Set& set : e.nw.sets) held += set.hs.cap + set.ck.cap;
-    budget = std::min<u64>((static_cast<u64>(free_b) + devpool::free_total()) / 4 + held, 64ULL << 30);  // parked blocks count as free
-    if (e.opt.nw_budget_mb > 0) budget = static_cast<u64>(e.opt.nw_budget_mb) << 20;
-    budget = std::max<u64>(budget, 64ULL << 20);
-  }
-  const bool trace_lds = !(knob("RVN_NW_TRACE_MEM") && std::atoi(knob("RVN_NW_TRACE_MEM")) == 1);
+  const u32 stripe_lanes;
+  const bool trace_lds;
   // which walk a launch takes (engine option nw_group_walk): 1 the lane per alignment with whole strips, 2 the group of lanes
   // per alignment, 3 the lane per alignment with strips of sixteen kept columns, otherwise by the number of alignments in the launch
-  const int group_walk = static_cast<int>(e.opt.nw_group_walk);
-  const bool one_stream = knob("RVN_NW_ONE_STREAM") != nullptr;
-  const bool dbg_sync = knob("RVN_NW_DEBUG") && std::atoi(knob("RVN_NW_DEBUG")) >= 2;
-  std::vector<double> rates;
-  rates.reserve(nj);  // (growing it inside collect() cost milliseconds of page faults with the GPU idle)
-  std::vector<u32> h_result(nj), h_status(nj);
-  constexpr u32 kHeadMax = 4096;  // jobs of the pass of the longest alignments (below)
-  NwJob* d_jobs = e.nw.jobs.get<NwJob>(static_cast<size_t>(nj) + 1 + 2 * kHeadMax);
-  u32* d_res = e.nw.res.get<u32>(3 * static_cast<size_t>(nj) + 32 + 6 * kHeadMax);
-  u32* d_status = d_res + nj + 1;
-  u32* d_idx = d_status + nj + 1;
-  u32* d_next = d_idx + nj + 1;
-  // A pass = a set of planned jobs queued together: its job records, order, results and states on the device.  The usual
-  // pass addresses them by job id; a COMPACT pass (the head, below) has arrays of its own, addressed by position in its order.
-  struct PassDev {
-    NwJob* jobs;
-    u32 *idx, *res, *status;
-    bool compact;
-  };
-  const PassDev dev_all{d_jobs, d_idx, d_res, d_status, false};
-  const PassDev dev_head{d_jobs + nj + 1, d_next + 4 + 2 * kHeadMax, d_next + 4, d_next + 4 + kHeadMax, true};
-  const PassDev dev_retry{dev_head.jobs + kHeadMax, dev_head.idx + 3 * kHeadMax, dev_head.res + 3 * kHeadMax,
-                          dev_head.status + 3 * kHeadMax, true};
-  u32* d_side_next = d_next + 4 + 6 * kHeadMax;  // (behind the compact passes' arrays) job counters of the sweeps launched beside the main stream, one per variant
-  bool side_pending[3] = {false, false, false};   // sweeps on a side stream that the main stream has not waited for yet
-  auto join_side = [&]() {
-    for (int x = 0; x < 3; ++x) {
-      if (side_pending[x]) RVN_HIP(hipStreamWaitEvent(s, e.nw.side_ev[x], 0));
-      side_pending[x] = false;
-    }
-  };
-  struct Obs {
-    double len, d;
-  };
-  using clk = std::chrono::steady_clock;
-  double h_plan = 0, h_order = 0, h_up = 0, h_res = 0;  // host milliseconds between the launches (RVN_NW_DEBUG)
-  auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-  std::vector<Obs> obs;
-  struct Chunk {
-    size_t c0, c1;
-    u64 hs_w, ck_e;
-    u32 coff[kClasses + 1];
-  };
+  const int group_walk;
+  const bool one_stream, dbg_sync;
+  const NwDevArrays dev;  // (dev.side_next: behind the compact passes' arrays)
+  bool side_pending[3] = {false, false, false};  // sweeps on a side stream that the main stream has not waited for yet
   bool set_used[4] = {false, false, false, false};  // a walk queued since the last collect() holds the buffer set
   struct Queued {  // what collect() reads back
     std::vector<u32> order;
-    PassDev dev;
+    NwPassDev dev;
     bool sweep_only;
     std::vector<u32> res, status;  // (compact passes)
   };
   std::vector<Queued> queued;
   std::vector<u8> early;  // job was handed to retry_early(): its state in the pass that found it stays "above the threshold"
+  std::vector<u32> h_result, h_status;
+  std::vector<double> rates;
+  std::vector<NwObs> obs;  // (length, distance) of the jobs of sweep-only passes: the pilot
+  double h_plan = 0, h_order = 0, h_up = 0, h_res = 0;  // host milliseconds between the launches (RVN_NW_DEBUG)
+
+  // the budget is taken before the call's arrays: it follows the free memory
+  NwRun(Engine& e_, const ReadsDev& T_, const ReadsDev& Rd_, std::vector<NwJob>& jobs_, u32 w_, NwWindowRec* d_recs_, NwPathSlots* path_,
+        NwStats& st_, std::vector<u32>* distances_)
+      : e(e_), T(T_), Rd(Rd_), jobs(jobs_), w(w_), d_recs(d_recs_), path(path_), st(st_), distances(distances_), s(e_.stream),
+        nj(static_cast<u32>(jobs_.size())), budget(nw_budget(e_)),
+        stripe_lanes(e_.opt.nw_stripe_lanes > 0 && e_.opt.nw_stripe_lanes < 64 ? static_cast<u32>(e_.opt.nw_stripe_lanes) : 64u),
+        trace_lds(!(knob("RVN_NW_TRACE_MEM") && std::atoi(knob("RVN_NW_TRACE_MEM")) == 1)),
+        group_walk(static_cast<int>(e_.opt.nw_group_walk)), one_stream(knob("RVN_NW_ONE_STREAM") != nullptr),
+        dbg_sync(knob("RVN_NW_DEBUG") && std::atoi(knob("RVN_NW_DEBUG")) >= 2), dev(arrays(e_, nj)), h_result(nj), h_status(nj) {
+    rates.reserve(nj);  // (growing it inside collect() cost milliseconds of page faults with the GPU idle)
+  }
+  static NwDevArrays arrays(Engine& e, u32 nj) {
+    const NwDevLayout at = nw_dev_layout(nj);
+    NwJob* d_jobs = e.nw.jobs.get<NwJob>(at.n_jobs);
+    return nw_dev_arrays(at, d_jobs, e.nw.res.get<u32>(at.n_words));
+  }
+
+  bool plan(NwJob& J, u64 k) const { return nw_plan(J, k, stripe_lanes, budget); }
+
+  void join_side() {
+    for (int x = 0; x < 3; ++x) {
+      if (side_pending[x]) RVN_HIP(hipStreamWaitEvent(s, e.nw.side_ev[x], 0));
+      side_pending[x] = false;
+    }
+  }
+
+  // a chunk's buffers and arrays, as its launches see them
+  struct ChunkDev {
+    const NwPassDev& dev;
+    int b;  // buffer set
+    u32* hs;
+    NwPm* ck;
+    u64* d_strip;
+    u32* d_slots;
+  };
+
+  template <class Out, class... Tail>
+  void launch_walk_kernel(void (*kernel)(const NwJob*, const u32*, u32, const u64*, const u64*, const u32*, const NwPm*, const u32*, u32*, u32,
+                                         Out*, Tail...),
+                          u32 per_block, const ChunkDev& c, Out* d_out, hipStream_t wst, const u32* idx_w, u32 n_w, Tail... tail) {
+    RVN_KLAUNCH_ON(kKNwTraceback, wst, (kernel<<<(n_w + per_block - 1) / per_block, 64, 0, wst>>>(
+                                           c.dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), c.hs, c.ck, c.dev.res,
+                                           c.dev.status, w, d_out, tail...)));
+  }
+  // Out — NwWindowRec: polishing; u32: the path form's slots
+  template <class Out>
+  void launch_walk_to(Out* d_out, const ChunkDev& c, hipStream_t wst, const u32* idx_w, u32 n_w) {
+    if (group_walk == 2 || (group_walk != 1 && n_w <= kNwGroupWalkMaxJobs)) {
+      // few alignments: a group of lanes each (nwtrace.h) — the walk of a few thousand alignments costs its longest one's
+      // latency, and a group walks a column in a fraction of a lane's time
+      launch_walk_kernel<Out>(nw_trace_group_kernel<kNwGroupLanes, Out>, 64 / kNwGroupLanes, c, d_out, wst, idx_w, n_w);
+    } else if (trace_lds && (group_walk == 3 || (group_walk != 1 && n_w > 64u * 4u * 256u))) {
+      // more waves than four per CU hold: strips of sixteen kept columns, nine waves per CU (C4: the walk of the last
+      // chunk's 140 000 shortest alignments, alone on the GPU, 18 -> 13 ms; align_ms 185 -> 174)
+      launch_walk_kernel<Out, u64*>(nw_trace_kernel<true, kNwLaneStripCols, Out>, 64, c, d_out, wst, idx_w, n_w, nullptr);
+    } else if (trace_lds) {
+      launch_walk_kernel<Out, u64*>(nw_trace_kernel<true, kNwCkSteps, Out>, 64, c, d_out, wst, idx_w, n_w, nullptr);
+    } else {
+      launch_walk_kernel<Out, u64*>(nw_trace_kernel<false, kNwCkSteps, Out>, 64, c, d_out, wst, idx_w, n_w,
+                                    c.d_strip + static_cast<size_t>(c.b) * ((e.nw.strip.cap / 32) & ~size_t(63)));
+    }
+  }
+  void launch_walk(const ChunkDev& c, hipStream_t wst, const u32* idx_w, u32 n_w) {
+    if (path) launch_walk_to(c.d_slots, c, wst, idx_w, n_w);
+    else launch_walk_to(d_recs, c, wst, idx_w, n_w);
+  }
+
+  // the sweep of the chunk's jobs of variant X, beside the main stream where side[X] says so
+  template <u32 X>
+  void launch_variant(const ChunkDev& c, const NwChunk& C, const u32* idx_c, const bool* side) {
+    constexpr int R = static_cast<int>(kNwVariants[X].R), G = static_cast<int>(kNwVariants[X].G);
+    const u32 n = nw_count_of(C, X);
+    launch_sweep<R, G>(e, side[X] ? e.nw.side[X % 3] : s, c.dev.jobs, idx_c + C.coff[X], n, T, Rd, c.hs, c.ck, c.dev.res, c.dev.status,
+                       side[X] ? dev.side_next + X : dev.next);
+    if (dbg_sync && n) {
+      RVN_HIP(hipStreamSynchronize(s));
+      std::fprintf(stderr, "[raven_hip] nw: sweep R=%d G=%d done, %u jobs\n", R, G, n);
+    }
+  }
+  template <u32 X = kLevels - 1>  // every variant of the table, widest first
+  void launch_variants(const ChunkDev& c, const NwChunk& C, const u32* idx_c, const bool* side) {
+    launch_variant<X>(c, C, idx_c, side);
+    if constexpr (X > 0) launch_variants<X - 1>(c, C, idx_c, side);
+  }
+
   // Queues the sweeps and walks of `todo` (already planned) and returns; collect() waits for everything queued and reads
-  // the results.  Chunk layout: kOwnFirst — the first chunk (the longest alignments) on buffer set 3 with a twelfth of the
-  // budget, the others on sets 0-2 in rotation with a third each; kHeadOnly — that first chunk ALONE, what does not fit it
-  // is handed back in `left`; kRotating — sets 0-2 only (the jobs behind a head that is already running).  up: the stream
-  // of the uploads (the host waits for them: not the engine's stream when a pass queued before is sweeping on it).
-  enum Layout { kOwnFirst, kHeadOnly, kRotating };
-  auto enqueue = [&](const std::vector<u32>& todo, bool sweep_only, Layout layout, const PassDev& dev, hipStream_t up,
-                     std::vector<u32>* left) {
+  // the results.  layout: nwplan.h (kHeadOnly hands what does not fit back in `left`).  up: the stream of the uploads (the
+  // host waits for them: not the engine's stream when a pass queued before is sweeping on it).
+  void enqueue(const std::vector<u32>& todo, bool sweep_only, NwLayout layout, const NwPassDev& pd, hipStream_t up, std::vector<u32>* left) {
     if (todo.empty()) return;
-    // longest jobs first: they go through the widest variants, and the pass ends with the walks of the shortest ones
     auto t_h = clk::now();
-    std::vector<u32> order;
-    {  // descending by (variant, columns), ties in job order: two counting passes (12 + 12 key bits) instead of a sort
-      const size_t nt = todo.size();
-      std::vector<u32> key(nt), tmp(nt), idx(nt);
-      parallel_for(nt, 16384, [&](size_t x0, size_t x1) {  // (the GPU waits for this planning: a few host threads)
-        for (size_t x = x0; x < x1; ++x) {
-          const NwJob& J = jobs[todo[x]];
-          // 8-base resolution is plenty for the ordering; striped jobs by their number of stripes (each stripe launch takes
-          // the jobs that have that stripe: a prefix of the class)
-          const u32 mm = J.S ? std::min<u32>(nw_geo_job(J).n_stripes, (1u << 20) - 1) : std::min<u32>(J.m >> 3, (1u << 20) - 1);
-          static_assert(kClasses <= 16, "4 bits of variant + 20 bits of length = the 24 key bits of the two passes");
-          key[x] = 0xFFFFFFu - ((level_of(J) << 20) | mm);
-          idx[x] = static_cast<u32>(x);
-        }
-      });
-      for (int pass = 0; pass < 2; ++pass) {
-        u32 cnt[4097] = {};
-        const int sh = 12 * pass;
-        for (size_t x = 0; x < nt; ++x) cnt[((key[idx[x]] >> sh) & 4095u) + 1]++;
-        for (int c = 0; c < 4096; ++c) cnt[c + 1] += cnt[c];
-        for (size_t x = 0; x < nt; ++x) tmp[cnt[(key[idx[x]] >> sh) & 4095u]++] = idx[x];
-        idx.swap(tmp);
-      }
-      order.resize(nt);
-      for (size_t x = 0; x < nt; ++x) order[x] = todo[idx[x]];
-    }
-    // chunks of the order whose hs + ck fit a third of the budget (a job larger than that goes alone).  (Capping the jobs
-    // per chunk — an even eighth, or a third of what is left, so that the uncovered walk of the last chunk gets shorter —
-    // was measured at C4 and did not pay: every extra sweep launch brings its own ramp and tail, +19 ms of sweep time
-    // against ~20 ms less at the end; profiles/r05_nw_timeline.csv.)
-    std::vector<Chunk> chunks;
-    u64 slot_w = 0;  // (path form) words of the pass's slots
-    struct Need {
-      u64 hw, ce, cells;
-      u32 level;
-    };
-    std::vector<Need> need(order.size());  // what a job stores and computes: per job in parallel, summed up in order below
-    parallel_for(order.size(), 16384, [&](size_t x0, size_t x1) {
-      for (size_t x = x0; x < x1; ++x) {
-        const NwJob& J = jobs[order[x]];
-        const NwGeo g = nw_geo_job(J);
-        need[x] = Need{g.hs_words(), g.ck_entries(), static_cast<u64>(J.m) * (static_cast<u64>(g.lo) + g.hi + 1), level_of(J)};
-      }
-    });
-    for (size_t c0 = 0; c0 < order.size();) {
-      Chunk C{};
-      C.c0 = c0;
-      size_t c1 = c0;
-      while (c1 < order.size()) {
-        NwJob& J = jobs[order[c1]];
-        const u64 hw = need[c1].hw, ce = need[c1].ce;
-        // three buffer sets in rotation + one of its own for the first chunk (the longest alignments: its walk is
-        // latency-bound — 106 ms for 2 432 alignments at C4 — and a set shared with chunk 3 made that chunk's sweep wait
-        // 17 ms for it), a quarter of a share
-        const u64 share = (chunks.empty() && layout != kRotating) ? budget / 12 : budget / 3;
-        if (c1 > c0 && (C.hs_w + hw) * 4 + (C.ck_e + ce) * 16 > share) break;
-        J.hs = C.hs_w;
-        J.ckpt = C.ck_e;
-        if (path && !sweep_only) {
-          J.bp_off = slot_w;
-          slot_w += nw_slot_words(J.k);
-        }
-        C.hs_w += hw;
-        C.ck_e += ce;
-        st.band_cells += need[c1].cells;
-        C.coff[need[c1].level + 1]++;
-        ++c1;
-      }
-      // the order is by descending level: offsets of the classes inside the chunk, in that order
-      u32 run_off = 0, cnt[kClasses];
-      for (u32 x = 0; x < kClasses; ++x) cnt[x] = C.coff[x + 1];
-      for (int x = static_cast<int>(kClasses) - 1; x >= 0; --x) {
-        C.coff[x] = run_off;
-        run_off += cnt[x];
-      }
-      C.coff[kClasses] = run_off;  // count of class x = offset of class x - 1 (or the chunk's end) - its own offset
-      C.c1 = c1;
-      st.store_bytes = std::max<u64>(st.store_bytes, C.hs_w * 4 + C.ck_e * 16);
-      chunks.push_back(C);
-      c0 = c1;
-      if (layout == kHeadOnly) break;
-    }
-    if (layout == kHeadOnly && chunks[0].c1 < order.size()) {  // what the head's share does not hold goes with the rest
-      for (size_t x = chunks[0].c1; x < order.size(); ++x) left->push_back(order[x]);
-      order.resize(chunks[0].c1);
-    }
-    // chunk 0 -> set 3 (its own), chunk ci >= 1 -> set (ci - 1) % 3;  kRotating: chunk ci -> set ci % 3
-    auto set_of = [&](size_t ci) -> int {
-      if (layout == kRotating) return static_cast<int>(ci % 3);
-      return ci == 0 ? 3 : static_cast<int>((ci - 1) % 3);
-    };
+    std::vector<u32> order = nw_order(jobs, todo);
+    const NwChunks cut = nw_chunks(order, jobs, budget, layout, path && !sweep_only, left);
+    const std::vector<NwChunk>& chunks = cut.chunks;
+    st.band_cells += cut.band_cells;
+    st.store_bytes = std::max<u64>(st.store_bytes, cut.store_bytes);
+    // every get() of the pass before any pointer into the blocks is taken: a get may move the block
     for (int b = 0; b < 4; ++b) {
       // sized for the chunks the set serves (a lone job beyond its share enlarges one set, not all)
-      u64 set_hs = 0, set_ck = 0;
-      bool used = false;
-      for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        if (set_of(ci) != b) continue;
-        used = true;
-        set_hs = std::max(set_hs, chunks[ci].hs_w);
-        set_ck = std::max(set_ck, chunks[ci].ck_e);
-      }
-      if (!used) continue;
-      (void)e.nw.sets[b].hs.get<u32>(set_hs + 4 * 64 * 8 + 16);  // + slack: the walk reads up to two words past a job's last one
-      (void)e.nw.sets[b].ck.get<NwPm>(set_ck + 16);
+      const NwSetNeed need = nw_set_need(chunks, layout, b);
+      if (!need.used) continue;
+      (void)e.nw.sets[b].hs.get<u32>(need.hs_w + 4 * 64 * 8 + 16);  // + slack: the walk reads up to two words past a job's last one
+      (void)e.nw.sets[b].ck.get<NwPm>(need.ck_e + 16);
     }
     u64* d_strip = nullptr;
     if (!trace_lds) {
       size_t mc = 0;
-      for (const Chunk& C : chunks) mc = std::max(mc, C.c1 - C.c0);
+      for (const NwChunk& C : chunks) mc = std::max(mc, C.c1 - C.c0);
       d_strip = e.nw.strip.get<u64>(static_cast<size_t>((mc + 63) / 64) * 2 * kNwStripCols * 64 * 4 + 64);
     }
     u32* d_slots = nullptr;
     if (path && !sweep_only) {
       path->blocks.emplace_back(new DevBuf());
-      d_slots = path->blocks.back()->get<u32>(slot_w + 16);
+      d_slots = path->blocks.back()->get<u32>(cut.slot_w + 16);
       for (u32 i : order) path->slot_end[i] = reinterpret_cast<u64>(d_slots + jobs[i].bp_off + nw_slot_words(jobs[i].k) - 1);
     }
     h_order += since(t_h);
     t_h = clk::now();
-    if (dev.compact) {  // records in the order of the pass, addressed by position
+    if (pd.compact) {  // records in the order of the pass, addressed by position
       std::vector<NwJob> hj(order.size());
       std::vector<u32> iota(order.size());
       for (size_t x = 0; x < order.size(); ++x) {
         hj[x] = jobs[order[x]];
         iota[x] = static_cast<u32>(x);
       }
-      RVN_HIP(hipMemcpyAsync(dev.jobs, hj.data(), hj.size() * sizeof(NwJob), hipMemcpyHostToDevice, up));
-      RVN_HIP(hipMemcpyAsync(dev.idx, iota.data(), iota.size() * 4, hipMemcpyHostToDevice, up));
+      RVN_HIP(hipMemcpyAsync(pd.jobs, hj.data(), hj.size() * sizeof(NwJob), hipMemcpyHostToDevice, up));
+      RVN_HIP(hipMemcpyAsync(pd.idx, iota.data(), iota.size() * 4, hipMemcpyHostToDevice, up));
       RVN_HIP(rvn_stream_sync(up));  // (locals)
     } else {
-      RVN_HIP(hipMemcpyAsync(dev.jobs, jobs.data(), static_cast<size_t>(nj) * sizeof(NwJob), hipMemcpyHostToDevice, up));
-      RVN_HIP(hipMemcpyAsync(dev.idx, order.data(), order.size() * 4, hipMemcpyHostToDevice, up));
+      RVN_HIP(hipMemcpyAsync(pd.jobs, jobs.data(), static_cast<size_t>(nj) * sizeof(NwJob), hipMemcpyHostToDevice, up));
+      RVN_HIP(hipMemcpyAsync(pd.idx, order.data(), order.size() * 4, hipMemcpyHostToDevice, up));
       RVN_HIP(rvn_stream_sync(up));  // `jobs` / `order` are pageable: the copies must be done before the host goes on
     }
     h_up += since(t_h);
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
-      const Chunk& C = chunks[ci];
-      const int b = set_of(ci);
-      u32* hs = e.nw.sets[b].hs.as<u32>();
-      NwPm* ck = e.nw.sets[b].ck.as<NwPm>();
-      const u32* idx_c = dev.idx + C.c0;
+      const NwChunk& C = chunks[ci];
+      const int b = nw_set_of(ci, layout);
+      const ChunkDev c{pd, b, e.nw.sets[b].hs.as<u32>(), e.nw.sets[b].ck.as<NwPm>(), d_strip, d_slots};
+      const u32* idx_c = pd.idx + C.c0;
       const u32 cn = static_cast<u32>(C.c1 - C.c0);
       // the walk that used this buffer set before (three chunks back in the rotation) is done with it
       if (set_used[b]) RVN_HIP(hipStreamWaitEvent(s, e.nw.ev[b], 0));
-      auto count_of = [&](u32 x) -> u32 {  // classes are laid out from the widest variant down
-        const u32 next_off = x == 0 ? cn : C.coff[x - 1];
-        return next_off - C.coff[x];
-      };
       // one walk stream per buffer set: the walk of the longest alignments (chunk 0: few waves, tens of milliseconds of
       // latency) must not hold back the walks of the chunks behind it
       hipStream_t ts = one_stream ? s : e.nw.streams[b];
-      auto launch_walk_to = [&](auto* d_out, hipStream_t wst, const u32* idx_w, u32 n_w) {
-        using Out = typename std::remove_pointer<decltype(d_out)>::type;  // NwWindowRec: polishing; u32: the path form's slots
-        if (group_walk == 2 || (group_walk != 1 && n_w <= kNwGroupWalkMaxJobs)) {
-          // few alignments: a group of lanes each (nwtrace.h) — the walk of a few thousand alignments costs its longest one's
-          // latency, and a group walks a column in a fraction of a lane's time
-          constexpr u32 NG = 64 / kNwGroupLanes;
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_group_kernel<kNwGroupLanes, Out><<<(n_w + NG - 1) / NG, 64, 0, wst>>>(
-                                                 dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_out)));
-        } else if (trace_lds && (group_walk == 3 || (group_walk != 1 && n_w > 64u * 4u * 256u))) {
-          // more waves than four per CU hold: strips of sixteen kept columns, nine waves per CU (C4: the walk of the last
-          // chunk's 140 000 shortest alignments, alone on the GPU, 18 -> 13 ms; align_ms 185 -> 174)
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwLaneStripCols, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
-                                                 dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_out, nullptr)));
-        } else if (trace_lds) {
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<true, kNwCkSteps, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
-                                                 dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_out, nullptr)));
-        } else {
-          RVN_KLAUNCH_ON(kKNwTraceback, wst, (nw_trace_kernel<false, kNwCkSteps, Out><<<(n_w + 63) / 64, 64, 0, wst>>>(
-                                                 dev.jobs, idx_w, n_w, T.packed.as<u64>(), Rd.packed.as<u64>(), hs, ck, dev.res,
-                                                 dev.status, w, d_out,
-                                                 d_strip + static_cast<size_t>(b) * ((e.nw.strip.cap / 32) & ~size_t(63)))));
-        }
-      };
-      auto launch_walk = [&](hipStream_t wst, const u32* idx_w, u32 n_w) {
-        if (path) launch_walk_to(d_slots, wst, idx_w, n_w);
-        else launch_walk_to(d_recs, wst, idx_w, n_w);
-      };
       // A variant's launch of few waves — the pilot's five, the several-blocks-per-lane variants of a round's longest
       // alignments (a few hundred jobs whose sweep is tens of thousands of dependent steps: 14-18 ms on 60-300 of the
       // machine's 6 000 wave slots) — runs BESIDE the others on a side stream instead of in front of them; the walk (and
@@ -688,11 +547,12 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       bool side_used[3] = {false, false, false};
       {
         u32 n_levels = 0;
-        for (u32 x = 0; x < kLevels; ++x) n_levels += count_of(x) ? 1u : 0u;
+        for (u32 x = 0; x < kLevels; ++x) n_levels += nw_count_of(C, x) ? 1u : 0u;
         if (n_levels >= 2 && !one_stream && !dbg_sync)
           for (u32 x = 0; x < kLevels; ++x) {
-            const u32 bundles = (count_of(x) + 64 / kGs[x] - 1) / (64 / kGs[x]);
-            side[x] = count_of(x) && bundles <= kSideSweepMaxWaves;
+            const u32 per_wave = 64 / kNwVariants[x].G;
+            const u32 bundles = (nw_count_of(C, x) + per_wave - 1) / per_wave;
+            side[x] = nw_count_of(C, x) && bundles <= kSideSweepMaxWaves;
             if (side[x]) side_used[x % 3] = true;
           }
         if (side_used[0] || side_used[1] || side_used[2]) {
@@ -701,7 +561,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
             if (side_used[y]) RVN_HIP(hipStreamWaitEvent(e.nw.side[y], e.nw.side_ev[3], 0));
         }
       }
-      if (const u32 n_str = count_of(kStriped)) {
+      if (const u32 n_str = nw_count_of(C, kStriped)) {
         // the striped jobs (the widest class: first in the chunk), stripe after stripe on the engine's stream — launch st
         // takes the jobs that have a stripe st, a prefix of the class (ordered by number of stripes)
         const u32* idx_s = idx_c + C.coff[kStriped];
@@ -711,31 +571,15 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
           u32 n_st = 0;
           while (n_st < n_str && n_stripes[n_st] > stp) ++n_st;
           if (n_st == 0) break;
-          launch_sweep<8, 64, true>(e, s, dev.jobs, idx_s, n_st, T, Rd, hs, ck, dev.res, dev.status, d_next, static_cast<int>(stp));
+          launch_sweep<static_cast<int>(kNwStripedVariant.R), static_cast<int>(kNwStripedVariant.G), true>(
+              e, s, pd.jobs, idx_s, n_st, T, Rd, c.hs, c.ck, pd.res, pd.status, dev.next, static_cast<int>(stp));
           if (dbg_sync) {
             RVN_HIP(hipStreamSynchronize(s));
             std::fprintf(stderr, "[raven_hip] nw: stripe %u done, %u jobs\n", stp, n_st);
           }
         }
       }
-#define RVN_SWEEP(x, R_, G_)                                                                                         \
-  do {                                                                                                               \
-    launch_sweep<R_, G_>(e, side[x] ? e.nw.side[(x) % 3] : s, dev.jobs, idx_c + C.coff[x], count_of(x), T, Rd, hs, ck, \
-                         dev.res, dev.status, side[x] ? d_side_next + (x) : d_next);                                   \
-    if (dbg_sync && count_of(x)) {                                                                                   \
-      RVN_HIP(hipStreamSynchronize(s));                                                                              \
-      std::fprintf(stderr, "[raven_hip] nw: sweep R=%d G=%d done, %u jobs\n", R_, G_, count_of(x));                   \
-    }                                                                                                                \
-  } while (0)
-      RVN_SWEEP(7, 8, 64);
-      RVN_SWEEP(6, 4, 64);
-      RVN_SWEEP(5, 2, 64);
-      RVN_SWEEP(4, 1, 64);
-      RVN_SWEEP(3, 1, 32);
-      RVN_SWEEP(2, 1, 16);
-      RVN_SWEEP(1, 1, 8);
-      RVN_SWEEP(0, 1, 4);
-#undef RVN_SWEEP
+      launch_variants(c, C, idx_c, side);
       for (int y = 0; y < 3; ++y)
         if (side_used[y]) {
           RVN_HIP(hipEventRecord(e.nw.side_ev[y], e.nw.side[y]));
@@ -749,7 +593,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         for (int y = 0; y < 3; ++y)
           if (side_used[y]) RVN_HIP(hipStreamWaitEvent(ts, e.nw.side_ev[y], 0));
       }
-      launch_walk(ts, idx_c, cn);
+      launch_walk(c, ts, idx_c, cn);
       if (!one_stream) {
         RVN_HIP(hipEventRecord(e.nw.ev[b], ts));
         set_used[b] = true;
@@ -759,11 +603,12 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         std::fprintf(stderr, "[raven_hip] nw: trace done, %u jobs\n", cn);
       }
     }
-    queued.push_back(Queued{std::move(order), dev, sweep_only, {}, {}});
-  };
+    queued.push_back(Queued{std::move(order), pd, sweep_only, {}, {}});
+  }
+
   // Waits for everything queued, reads the results; the jobs beyond their thresholds come back in `again` (planned with
   // twice the band and the variant that holds it).
-  auto collect = [&](std::vector<u32>& again) {
+  void collect(std::vector<u32>& again) {
     again.clear();
     join_side();
     for (int b = 0; b < 4; ++b) {  // (an event stands for the LAST walk recorded on its set)
@@ -778,8 +623,8 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         RVN_HIP(hipMemcpyAsync(q.status.data(), q.dev.status, q.order.size() * 4, hipMemcpyDeviceToHost, s));
       }
     }
-    RVN_HIP(hipMemcpyAsync(h_result.data(), d_res, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
-    RVN_HIP(hipMemcpyAsync(h_status.data(), d_status, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
+    RVN_HIP(hipMemcpyAsync(h_result.data(), dev.all.res, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
+    RVN_HIP(hipMemcpyAsync(h_status.data(), dev.all.status, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
     RVN_HIP(rvn_stream_sync(s));
     auto t_h = clk::now();
     for (const Queued& q : queued)
@@ -790,7 +635,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         }
     for (size_t qi = 0; qi < queued.size(); ++qi) {
       const Queued& q = queued[qi];
-      const bool is_early_retry = q.dev.jobs == dev_retry.jobs;
+      const bool is_early_retry = q.dev.jobs == dev.retry.jobs;
       // the aligned jobs of a pass (all but a handful) are only counted: on a few threads — the pass order is by length,
       // i.e. random in the 28 MB of job records, and one thread's cache misses were ~10 ms with the GPU idle
       std::vector<u32> rest_of;  // everything that is not a plain "aligned"
@@ -798,7 +643,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         rest_of = q.order;
       } else {
         std::mutex mu_;
-        parallel_for(q.order.size(), 16384, [&](size_t x0, size_t x1) {
+        parallel_for(q.order.size(), 16384, [this, &q, &mu_, &rest_of, is_early_retry](size_t x0, size_t x1) {
           u64 n_al = 0, sum_d = 0;
           std::vector<double> rr;
           std::vector<u32> other;
@@ -833,20 +678,21 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         } else if (h_status[i] != 0) {
           throw HipError("[raven_hip] alignment path: the walk left the stored band (internal error)");
         } else {  // (a sweep-only pass: the pilot)
-          obs.push_back(Obs{static_cast<double>(std::max(J.n, J.m)), static_cast<double>(h_result[i])});
+          obs.push_back(NwObs{static_cast<double>(std::max(J.n, J.m)), static_cast<double>(h_result[i])});
         }
       }
     }
     early.clear();
     queued.clear();
     h_res += since(t_h);
-  };
+  }
+
   // Whether an alignment is beyond its threshold is known when its SWEEP is done: the states are read once the sweeps of
   // everything queued are through — the last walks still run on their streams — and the few jobs above their thresholds
   // (two or three of 295 000 at C4) are planned again and queued at once, as a compact pass on the head's buffer set,
   // instead of as a pass of their own behind the last walk (~9 ms per round of sweep + lonely walk + host round trips,
   // profiles/r05_nw_timeline.csv).  A job handed on here is skipped by collect() in the pass that found it.
-  auto retry_early = [&]() {
+  void retry_early() {
     if (one_stream || queued.empty()) return;
     join_side();
     for (Queued& q : queued)
@@ -854,7 +700,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
         q.status.resize(q.order.size());
         RVN_HIP(hipMemcpyAsync(q.status.data(), q.dev.status, q.order.size() * 4, hipMemcpyDeviceToHost, s));
       }
-    RVN_HIP(hipMemcpyAsync(h_status.data(), d_status, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
+    RVN_HIP(hipMemcpyAsync(h_status.data(), dev.all.status, static_cast<size_t>(nj) * 4, hipMemcpyDeviceToHost, s));
     RVN_HIP(rvn_stream_sync(s));  // (the sweeps; not the walks)
     std::vector<u32> todo;
     for (const Queued& q : queued)
@@ -879,124 +725,89 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
     // (set 3 may have to grow for a doubled band, and growing hands the old block back: the walk on it — the head's, queued
     // long before — must be through)
     if (set_used[3]) RVN_HIP(hipEventSynchronize(e.nw.ev[3]));
-    enqueue(todo, false, kHeadOnly, dev_retry, e.nw.streams[4], &left);
+    enqueue(todo, false, kHeadOnly, dev.retry, e.nw.streams[4], &left);
     for (u32 i : left) early[i] = 0;  // (beyond the set's share: their doubled plan stands, collect() doubles it once more)
     st.n_retries -= left.size();
-  };
+  }
+
   // aligns every job of `todo` (already planned), repeating the ones beyond their threshold with twice the band
-  auto run = [&](std::vector<u32> todo, bool sweep_only) {
+  void run(std::vector<u32> todo, bool sweep_only) {
     while (!todo.empty()) {
-      enqueue(todo, sweep_only, kOwnFirst, dev_all, s, nullptr);
+      enqueue(todo, sweep_only, kOwnFirst, dev.all, s, nullptr);
       std::vector<u32> again;
       collect(again);
       todo.swap(again);
     }
-  };
+  }
+};
 
-  // Thresholds.  A pilot sample (every call: the error level changes from round to round) is aligned with a generous
-  // band; its distances give the mean rate mu and the spread around mu x len as  var = a len + b len^2  (a: base-level
-  // noise, b: differences between reads).  Everyone gets  k = mu len + 4.5 sqrt(a len + b len^2) + 6 : with a normal
-  // spread a few alignments in a million are repeated (a repeat pass ends with lonely, latency-bound walks, so it is
-  // worth ~3 % more band to make it rare), against one in ten with a 90th-percentile rule.  The pilot is swept for its
-  // distances only and skips the longest quarter of the reads.  Small batches keep the previous call's estimate.
+}  // namespace
+
+// Fills the band fields of `jobs` (k, kcap, R, G, hs, ckpt) and produces every job's window records in d_recs
+// (records of a job start at its bp_off; jobs that cannot be aligned keep all-invalid records and are counted).
+// What is decided here is in nwplan.h, how it is launched in NwRun above; this is the schedule of a call.
+void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vector<NwJob>& jobs, u32 w,
+                    NwWindowRec* d_recs, u64 n_recs, NwStats& st, std::vector<u32>* distances, NwPathSlots* path) {
+  st = NwStats();
+  const u32 nj = static_cast<u32>(jobs.size());
+  if (distances) distances->assign(nj, ~0u);
+  if (path) path->slot_end.assign(nj, 0);
+  hipStream_t s = e.stream;
+  if (n_recs) RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
+  if (nj == 0) return;
+  RVN_HIP(hipEventRecord(e.ev0, s));
+  if (!e.nw.streams[0]) e.nw.open();
+  WalkGuard walk_guard{e};
+  double rate = e.nw.rate > 0 ? e.nw.rate : 0.13;  // first call: ONT-like; too small only costs a repeat
+  if (const char* ev = knob("RVN_NW_RATE")) rate = std::atof(ev);  // (debug builds: force repeats)
+  std::vector<u32> valid;
+  for (u32 i = 0; i < nj; ++i) {
+    const NwJob& J = jobs[i];
+    if (J.n == 0 || J.m == 0 || J.n >= (1u << 30) || J.m >= (1u << 30)) ++st.n_unaligned;
+    else valid.push_back(i);
+  }
+  NwRun pass(e, T, Rd, jobs, w, d_recs, path, st, distances);  // (the budget, the call's device arrays)
+
+  // Thresholds (nwplan.h: NwThresholdModel): a pilot sample, swept for its distances only, gives the model everyone's
+  // threshold comes from.  Small batches keep the previous call's estimate.
   std::vector<u32> rest, head;
-  double mu = -1, va = 0, vb = 0;
+  NwThresholdModel model;
   if (valid.size() >= 4096 && !knob("RVN_NW_RATE")) {
-    std::vector<u32> lens;
-    for (u32 i : valid) lens.push_back(std::max(jobs[i].n, jobs[i].m));
-    std::nth_element(lens.begin(), lens.begin() + lens.size() * 3 / 4, lens.end());
-    const u32 len_cap = lens[lens.size() * 3 / 4];
-    std::vector<u32> pilot;
-    const size_t stride = valid.size() / 1400;
-    for (size_t x = 0; x < valid.size(); ++x) {
-      const NwJob& J = jobs[valid[x]];
-      if (x % stride == stride / 2 && pilot.size() < 1024 && std::max(J.n, J.m) <= len_cap) pilot.push_back(valid[x]);
-      rest.push_back(valid[x]);  // the pilot is swept for its distances only; its jobs are aligned with everyone else
-    }
+    rest = valid;  // the pilot is swept for its distances only; its jobs are aligned with everyone else
     std::vector<u32> ok;
-    for (u32 i : pilot) {
-      NwJob& J = jobs[i];
-      if (plan(J, static_cast<u64>((rate * 1.25 + 0.02) * std::max(J.n, J.m)) + 16)) ok.push_back(i);
-    }
-    enqueue(ok, true, kOwnFirst, dev_all, s, nullptr);
+    for (u32 i : nw_pilot_sample(jobs, valid))
+      if (pass.plan(jobs[i], NwThresholdModel::pilot_threshold(nw_job_len(jobs[i]), rate))) ok.push_back(i);
+    pass.enqueue(ok, true, kOwnFirst, pass.dev.all, s, nullptr);
     // (while the pilot is swept) the longest alignments: they go first and by themselves, see below
-    if (!one_stream) {
-      const size_t n_head = std::min<size_t>(kHeadMax, rest.size() / 8);
-      auto longer = [&](u32 x, u32 y) {
-        const u32 lx = std::max(jobs[x].n, jobs[x].m), ly = std::max(jobs[y].n, jobs[y].m);
-        return lx != ly ? lx > ly : x < y;
-      };
-      std::nth_element(rest.begin(), rest.begin() + n_head, rest.end(), longer);
-      head.assign(rest.begin(), rest.begin() + n_head);
-      rest.erase(rest.begin(), rest.begin() + n_head);
-    }
+    if (!pass.one_stream) nw_take_head(jobs, rest, head);
     {
       std::vector<u32> again;
-      collect(again);
-      run(again, true);
+      pass.collect(again);
+      pass.run(again, true);
     }
-    if (obs.size() >= 256) {
-      double sl = 0, sd = 0;
-      for (const Obs& o : obs) {
-        sl += o.len;
-        sd += o.d;
-      }
-      mu = sd / sl;
-      // least squares of the squared residuals on (len, len^2), the 2 % largest standardised residuals left out
-      std::vector<double> zs;
-      for (const Obs& o : obs) zs.push_back(std::fabs(o.d - mu * o.len) / std::sqrt(o.len));
-      std::vector<double> zsorted = zs;
-      std::sort(zsorted.begin(), zsorted.end());
-      const double zcut = zsorted[static_cast<size_t>(zsorted.size() * 0.98)];
-      double s11 = 0, s12 = 0, s22 = 0, t1 = 0, t2 = 0, sr = 0, sn = 0;
-      for (size_t x = 0; x < obs.size(); ++x) {
-        if (zs[x] > zcut) continue;
-        const double L = obs[x].len * 1e-3, r2 = (obs[x].d - mu * obs[x].len) * (obs[x].d - mu * obs[x].len);
-        s11 += L * L;
-        s12 += L * L * L;
-        s22 += L * L * L * L;
-        t1 += r2 * L;
-        t2 += r2 * L * L;
-        sr += r2 / L;
-        sn += 1;
-      }
-      const double det = s11 * s22 - s12 * s12;
-      double a = -1, b = -1;
-      if (det > 1e-9 * s11 * s22) {
-        a = (t1 * s22 - t2 * s12) / det;
-        b = (t2 * s11 - t1 * s12) / det;
-      }
-      if (!(a >= 0) || !(b >= 0)) {  // one length only, or a fit outside the model: all spread on the linear term
-        a = sn > 0 ? sr / sn : mu * 1e3;
-        b = 0;
-      }
-      va = std::max(a * 1e-3, 0.25 * mu);  // back to bases; never below a quarter of the Poisson level
-      vb = b * 1e-6;
-    }
+    model.fit(pass.obs);
   } else {
     rest = valid;
   }
   {
     auto t_h = clk::now();
-    auto threshold = [&](const NwJob& J) -> u64 {
-      const double len = std::max(J.n, J.m);
-      const double z = 4.5;
-      return mu > 0 ? static_cast<u64>(mu * len + z * std::sqrt(va * len + vb * len * len)) + 6 : static_cast<u64>(rate * len) + 16;
-    };
     // The longest alignments are a pass of their own, queued the moment the thresholds exist: planning, ordering and
     // uploading 300 000 jobs took the host ~20 ms in which the GPU did nothing (profiles/r05_nw_timeline.csv: 6.6 -> 28.7 ms),
     // every round; now the head's sweeps (~23 ms at C4) run in that time, and its walk — the long pole, one lane per
     // alignment — starts that much earlier.  (Results do not depend on which pass or chunk a job is in.)
     std::vector<u32> ok_head, left;
     for (u32 i : head) {
-      if (plan(jobs[i], threshold(jobs[i]))) ok_head.push_back(i);
+      if (pass.plan(jobs[i], model.threshold(nw_job_len(jobs[i]), rate))) ok_head.push_back(i);
       else ++st.n_unaligned;
     }
     const bool split = !ok_head.empty();
-    if (split) enqueue(ok_head, false, kHeadOnly, dev_head, s, &left);
+    if (split) pass.enqueue(ok_head, false, kHeadOnly, pass.dev.head, s, &left);
     std::vector<u8> planned(rest.size());
-    parallel_for(rest.size(), 16384, [&](size_t x0, size_t x1) {
-      for (size_t x = x0; x < x1; ++x) planned[x] = plan(jobs[rest[x]], threshold(jobs[rest[x]])) ? 1 : 0;
+    parallel_for(rest.size(), 16384, [&jobs, &rest, &planned, &model, rate, sl = pass.stripe_lanes, budget = pass.budget](size_t x0, size_t x1) {
+      for (size_t x = x0; x < x1; ++x) {
+        NwJob& J = jobs[rest[x]];
+        planned[x] = nw_plan(J, model.threshold(nw_job_len(J), rate), sl, budget) ? 1 : 0;
+      }
     });
     std::vector<u32> ok;
     ok.reserve(rest.size() + left.size());
@@ -1005,30 +816,27 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
       else ++st.n_unaligned;
     }
     ok.insert(ok.end(), left.begin(), left.end());
-    h_plan += since(t_h);
-    enqueue(ok, false, split ? kRotating : kOwnFirst, dev_all, split ? e.nw.streams[4] : s, nullptr);
-    retry_early();
+    pass.h_plan += since(t_h);
+    pass.enqueue(ok, false, split ? kRotating : kOwnFirst, pass.dev.all, split ? e.nw.streams[4] : s, nullptr);
+    pass.retry_early();
     std::vector<u32> again;
-    collect(again);
-    run(again, false);
+    pass.collect(again);
+    pass.run(again, false);
   }
   RVN_HIP(hipEventRecord(e.ev1, s));
-  if (rates.size() >= 32) {  // rate estimate for the next call (the pilot's first threshold / small batches)
-    const size_t at = std::min(rates.size() - 1, static_cast<size_t>(rates.size() * 0.9));
-    std::nth_element(rates.begin(), rates.begin() + at, rates.end());  // (the order statistic a full sort gave: ~15 ms of host time per round)
-    e.nw.rate = rates[at] * 1.05 + 0.002;
-  }
+  e.nw.rate = nw_next_rate(pass.rates, e.nw.rate);
   RVN_HIP(hipEventSynchronize(e.ev1));
   float ms = 0;
   RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
   st.ms = ms;
   if (knob("RVN_NW_DEBUG"))
-    std::fprintf(stderr, "[raven_hip] nw host: plan %.1f ms, order + chunks %.1f ms, uploads %.1f ms, results %.1f ms\n", h_plan, h_order, h_up,
-                 h_res);
+    std::fprintf(stderr, "[raven_hip] nw host: plan %.1f ms, order + chunks %.1f ms, uploads %.1f ms, results %.1f ms\n", pass.h_plan, pass.h_order,
+                 pass.h_up, pass.h_res);
   if (knob("RVN_NW_DEBUG"))
     std::fprintf(stderr, "[raven_hip] nw: %u jobs, %llu aligned, %llu retries, %llu chunks, %.3e band cells, %.1f MB hs + ck, %.1f ms; pilot mu %.4f a %.4f b %.3e\n", nj,
                  static_cast<unsigned long long>(st.n_aligned), static_cast<unsigned long long>(st.n_retries),
-                 static_cast<unsigned long long>(st.n_batches), static_cast<double>(st.band_cells), st.store_bytes / 1048576.0, ms, mu, va, vb);
+                 static_cast<unsigned long long>(st.n_batches), static_cast<double>(st.band_cells),
+                 st.store_bytes / 1048576.0, ms, model.mu, model.va, model.vb);
 }
 
 // ---- the path form: the walkers' runs, dense and in pair order; edlib's one byte per op ----------------------------------
@@ -1382,23 +1190,23 @@ int nw_breakpoints_host(const u64* t_words, u32 t_len, const u64* r_words, u32 r
   }
   u32 lvl = 0;
   if (force_R >= 1000) {  // R * 1000 + G: one particular variant
-    while (lvl < kLevels && !(kRs[lvl] == static_cast<u32>(force_R / 1000) && kGs[lvl] == static_cast<u32>(force_R % 1000))) ++lvl;
+    while (lvl < kLevels && !(kNwVariants[lvl].R == static_cast<u32>(force_R / 1000) && kNwVariants[lvl].G == static_cast<u32>(force_R % 1000))) ++lvl;
     if (lvl == kLevels) return -2;
   } else if (force_R > 0) {  // that many blocks per lane, whole-wave ring
-    while (lvl < kLevels && !(kRs[lvl] == static_cast<u32>(force_R) && kGs[lvl] == 64)) ++lvl;
+    while (lvl < kLevels && !(kNwVariants[lvl].R == static_cast<u32>(force_R) && kNwVariants[lvl].G == 64)) ++lvl;
     if (lvl == kLevels) return -2;
   } else if (force_R < 0) {  // one block per lane, ring of at most -force_R lanes
-    while (lvl < kLevels && !(kRs[lvl] == 1 && kGs[lvl] == static_cast<u32>(-force_R))) ++lvl;
+    while (lvl < kLevels && !(kNwVariants[lvl].R == 1 && kNwVariants[lvl].G == static_cast<u32>(-force_R))) ++lvl;
     if (lvl == kLevels) return -2;
   }
   for (; lvl < kLevels; ++lvl) {
-    const u32 cap = kcap_of(n, m, kRs[lvl], kGs[lvl]);
+    const u32 cap = kcap_of(n, m, kNwVariants[lvl].R, kNwVariants[lvl].G);
     if (cap < kk) {
       if (force_R) return -2;
       continue;
     }
-    J.R = kRs[lvl];
-    J.G = kGs[lvl];
+    J.R = kNwVariants[lvl].R;
+    J.G = kNwVariants[lvl].G;
     J.k = static_cast<u32>(kk);
     J.kcap = cap;
     int rcode;
