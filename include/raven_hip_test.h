@@ -149,6 +149,29 @@ int rvn_test_engine_scratch_bytes(rvn_engine* h, uint64_t* bytes);
 int rvn_test_best_overlap(const rvn_overlap* overlaps, uint64_t n_overlaps, const uint32_t* read_off, uint32_t first,
                           uint32_t n, double err_thr, const uint32_t* id_to_target, uint32_t n_ids, rvn_overlap* best,
                           uint32_t* best_target, uint32_t n_rows);
+/* The second mapping pass (pass2.hip) ON THE DEVICE with Map's output of every batch taken from the host: runs
+ * second_pass_prepare, then for every batch the part of second_pass_batch that follows Map (second_pass_merge: AddKmers of
+ * the filtered positions, OverlapUpdate, the identity filter, type and containment flags, survivors appended), then
+ * second_pass_finish — the functions the product calls; no kernel is launched from the hook.  h / reads: an engine and an
+ * uploaded read set of THIS library (ids[i] == i); pile_begin / pile_end (bases, begin <= end <= length) / pile_invalid
+ * as rvn_find_overlaps_and_repetitive_regions.  A batch: the query reads [q_first, q_last) counted among the VALID reads
+ * (ascending id), their sketch as the kernel sees it — q_origins[n_query] (id << 32 | pos << 1 | strand; pos <= length -
+ * kmer_len), q_read_off[q_last - q_first + 1] ascending from 0 to n_query, filtered[n_query] flags (0 / 1) — and Map's
+ * overlaps in (query read, emission) order (ids < n).  No pile invalid, or every pile: as the product, nothing runs.
+ * *out: a result for rvn_pass2_num_overlaps / _kmer_cells / _fetch / _destroy.  RVN_EINVAL for a NULL argument, ids or
+ * positions out of range, offsets that do not ascend, kmer_len outside [1, 32], identity outside [0, 1]. */
+typedef struct rvn_test_pass2_batch {
+  uint32_t q_first, q_last;
+  const uint64_t* q_origins;
+  const uint32_t* q_read_off;
+  const uint8_t* filtered;
+  uint64_t n_query;
+  const rvn_overlap* overlaps;
+  uint64_t n_overlaps;
+} rvn_test_pass2_batch;
+int rvn_test_second_pass(rvn_engine* h, const rvn_reads* reads, const uint32_t* pile_begin, const uint32_t* pile_end,
+                         const uint8_t* pile_invalid, double identity, uint32_t kmer_len,
+                         const rvn_test_pass2_batch* batches, uint32_t n_batches, rvn_pass2** out);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

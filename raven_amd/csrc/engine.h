@@ -465,6 +465,9 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
                          u64 batch_bases, Pass2State& out, Pass2Prep& P);
 u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first, u32 q_last, double freq, u32 kmer_len,
                       double identity, Pass2State& out);
+// its part behind Map: AddKmers, update_and_identity, classify, compaction, append (mo = Map's output for the query reads)
+u64 second_pass_merge(Engine& e, Pass2Prep& P, u32 q_first, u32 q_last, const MapOut& mo, u32 kmer_len, double identity,
+                      Pass2State& out);
 void second_pass_finish(Engine& e, PileRegion* d_regions, Pass2State& out);
 void or_bytes(Engine& e, u8* d_dst, const u8* d_src, u64 n);  // d_dst[i] |= d_src[i]
 void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_off, const u32* h_begin, const u32* h_end,

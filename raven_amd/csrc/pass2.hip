@@ -21,6 +21,10 @@
 #include "lowcomplexity.h"
 #include "overlap_rules.h"
 #include "wave.h"
+#ifdef RVN_TEST_HOOKS
+#include "../../include/raven_hip_test.h"
+#include "abi.h"
+#endif
 
 namespace rvn {
 
@@ -343,19 +347,14 @@ void second_pass_prepare(Engine& e, const ReadsDev& R, const u32* h_begin, const
   }
 }
 
-// Index batch [first, last) of the valid reads; the query reads [q_first, q_last) (inside [0, last)) are mapped against it
-// (the reference maps all of [0, last): construct.cc:362-383), their k-mer cells filled, their overlaps updated,
-// identity-filtered, classified and appended to out.ovl.  Returns the number appended.
-u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first, u32 q_last, double freq, u32 kmer_len,
-                      double identity, Pass2State& out) {
+// What follows the Map of the query reads [q_first, q_last) in an index batch: `mo` is Map's output for them (overlaps in
+// (query read, emission) order, `filtered` flags of the query sketch, which is e.sketch.query_sketch).  AddKmers of the
+// filtered positions, OverlapUpdate, the identity filter, type, containment flags, survivors appended to out.ovl.
+// Returns the number appended.
+u64 second_pass_merge(Engine& e, Pass2Prep& P, u32 q_first, u32 q_last, const MapOut& mo, u32 kmer_len, double identity,
+                      Pass2State& out) {
   hipStream_t s = e.stream;
-  if (q_first >= q_last) return 0;
   const ReadsDev& V = P.V;
-  engine_minimize(e, V, first, last, false);
-  index_filter(e, freq);
-  MapOut& mo = e.map.out;
-  map_batch(e, V, q_first, q_last, true, true, false, true, mo);
-  e.c_intervals += mo.n_intervals;
   // Pile::AddKmers(filtered, kmer_len, sequence) of every mapped read (construct.cc:382)
   if (mo.n_query) {
     RVN_KLAUNCH(kKAddKmers, add_kmers_flags_kernel<<<div_up(mo.n_query, 256), 256, 0, s>>>(
@@ -380,6 +379,21 @@ u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first,
   compact_overlaps(e, d_ovl, d_keep, ks.slot, O, out.ovl.as<Overlap>() + acc_n);
   out.n_overlaps = acc_n + m;
   return m;
+}
+
+// Index batch [first, last) of the valid reads; the query reads [q_first, q_last) (inside [0, last)) are mapped against it
+// (the reference maps all of [0, last): construct.cc:362-383), their k-mer cells filled, their overlaps updated,
+// identity-filtered, classified and appended to out.ovl.  Returns the number appended.
+u64 second_pass_batch(Engine& e, Pass2Prep& P, u32 first, u32 last, u32 q_first, u32 q_last, double freq, u32 kmer_len,
+                      double identity, Pass2State& out) {
+  if (q_first >= q_last) return 0;
+  const ReadsDev& V = P.V;
+  engine_minimize(e, V, first, last, false);
+  index_filter(e, freq);
+  MapOut& mo = e.map.out;
+  map_batch(e, V, q_first, q_last, true, true, false, true, mo);
+  e.c_intervals += mo.n_intervals;
+  return second_pass_merge(e, P, q_first, q_last, mo, kmer_len, identity, out);
 }
 
 // After the last batch, on the list in the reference's merge order: consecutive overlaps of the same pair keep the longer
@@ -460,4 +474,92 @@ void identity_filter_lists(Engine& e, const ReadsDev& R, Overlap* h_ovl, u32* h_
   identity_filter_compact(h_ovl, h_off, n, ok.data(), upd.data());
 }
 
+#ifdef RVN_TEST_HOOKS
+// rvn_test_second_pass (include/raven_hip_test.h): second_pass with the Map output of every batch taken from the host.
+// Every argument that a kernel would index with is checked here, for all batches, before the first launch; no kernel is
+// launched from here.  It leaves e.sketch.query_sketch and e.map.out fabricated (counts and offsets of the last batch, no
+// minimizer values, no matches): the engine must not Map afterwards without a fresh engine_minimize / map_batch.
+static void test_second_pass(Engine& e, const ReadsDev& R, const u32* h_begin, const u32* h_end, const u8* h_invalid,
+                             double identity, u32 kmer_len, const rvn_test_pass2_batch* batches, u32 n_batches,
+                             Pass2State& out) {
+  auto bad = [](const char* what) { throw std::invalid_argument(std::string("[raven_hip] rvn_test_second_pass: ") + what); };
+  if (kmer_len == 0 || kmer_len > 32) bad("kmer_len must be in [1, 32]");
+  if (!(0 <= identity && identity <= 1)) bad("identity must be in [0, 1]");
+  std::vector<u32> valid;  // as second_pass_prepare orders them: the valid reads by id
+  for (u32 i = 0; i < R.n; ++i) {
+    if (R.h_id[i] != i) bad("requires ids[i] == i");
+    if (h_begin[i] > h_end[i] || h_end[i] > R.h_len[i]) bad("a valid region outside its read");
+    if (!h_invalid[i]) valid.push_back(i);
+  }
+  // (as second_pass: with every pile valid or every pile invalid nothing is mapped and no batch is looked at)
+  const u32 sv = valid.size() == R.n ? 0u : static_cast<u32>(valid.size());
+  for (u32 b = 0; sv && b < n_batches; ++b) {
+    const rvn_test_pass2_batch& B = batches[b];
+    if (B.q_first > B.q_last || B.q_last > sv) bad("query reads outside the valid reads");
+    const u32 nr = B.q_last - B.q_first;
+    const u64 nq = B.n_query, O = B.n_overlaps;
+    if (nq >= (1ULL << 32) || O >= (1ULL << 32)) bad(">= 2^32 entries in a batch");
+    if (!B.q_read_off || (nq && (!B.q_origins || !B.filtered)) || (O && !B.overlaps)) bad("NULL array in a batch");
+    if (B.q_read_off[0] != 0 || B.q_read_off[nr] != nq) bad("offsets must run from 0 to n_query");
+    if (nr == 0 && O) bad("overlaps in a batch without query reads");
+    for (u32 r = 0; r < nr; ++r) {
+      if (B.q_read_off[r + 1] < B.q_read_off[r] || B.q_read_off[r + 1] > nq) bad("offsets must ascend to n_query");
+      const u32 len = R.h_len[valid[B.q_first + r]];
+      for (u64 q = B.q_read_off[r]; q < B.q_read_off[r + 1]; ++q) {
+        if (B.filtered[q] > 1) bad("filtered flags are 0 or 1");
+        if (len < kmer_len || (static_cast<u32>(B.q_origins[q]) >> 1) > len - kmer_len) bad("a k-mer beyond its read");
+      }
+    }
+    for (u64 x = 0; x < O; ++x)
+      if (B.overlaps[x].lhs_id >= R.n || B.overlaps[x].rhs_id >= R.n) bad("overlap id out of range");
+  }
+  Pass2Prep P;
+  second_pass_prepare(e, R, h_begin, h_end, h_invalid, 1ULL << 30, out, P);
+  if (P.sv == 0) return;
+  hipStream_t s = e.stream;
+  for (u32 b = 0; b < n_batches; ++b) {
+    const rvn_test_pass2_batch& B = batches[b];
+    const u32 nr = B.q_last - B.q_first;
+    const u64 nq = B.n_query, O = B.n_overlaps;
+    if (nr == 0) continue;  // (no query reads, hence no overlaps: checked above)
+    Sketch& qs = e.sketch.query_sketch;
+    e.sketch.query_ready = {};
+    qs.first = B.q_first;
+    qs.last = B.q_last;
+    qs.count = nq;
+    MapOut& mo = e.map.out;
+    mo.first = B.q_first;
+    mo.last = B.q_last;
+    mo.n_query = nq;
+    mo.n_matches = mo.n_intervals = 0;
+    mo.n_overlaps = O;
+    mo.has_anchors = false;
+    upload(qs.org, B.q_origins, nq, s);
+    upload(qs.read_off, B.q_read_off, static_cast<size_t>(nr) + 1, s);
+    upload(mo.filtered, B.filtered, nq, s);
+    upload(mo.ovl, reinterpret_cast<const Overlap*>(B.overlaps), O, s);
+    RVN_HIP(rvn_stream_sync(s));
+    second_pass_merge(e, P, B.q_first, B.q_last, mo, kmer_len, identity, out);
+  }
+  second_pass_finish(e, P.d_regions, out);
+}
+#endif  // RVN_TEST_HOOKS
+
 }  // namespace rvn
+
+#ifdef RVN_TEST_HOOKS
+extern "C" int rvn_test_second_pass(rvn_engine* h, const rvn_reads* rr, const uint32_t* pile_begin, const uint32_t* pile_end,
+                                    const uint8_t* pile_invalid, double identity, uint32_t kmer_len,
+                                    const rvn_test_pass2_batch* batches, uint32_t n_batches, rvn_pass2** out) {
+  using namespace rvn;
+  const bool ok = h && rr && out && !(rr->r.n && (!pile_begin || !pile_end || !pile_invalid)) && !(n_batches && !batches);
+  return guarded(h, ok, "[raven_hip] rvn_test_second_pass: NULL argument", [&](Engine& e) -> int {
+    std::unique_ptr<rvn_pass2> p(new rvn_pass2());
+    p->e = &e;
+    p->engine_life = e.life;
+    test_second_pass(e, rr->r, pile_begin, pile_end, pile_invalid, identity, kmer_len, batches, n_batches, p->st);
+    *out = p.release();
+    return RVN_OK;
+  });
+}
+#endif  // RVN_TEST_HOOKS

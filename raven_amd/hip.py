@@ -214,6 +214,7 @@ _TEST_SIGNATURES = {
     "rvn_test_compact_overlap_list": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "rvn_test_engine_scratch_bytes": (_i32, [_vp, _pu64]),
     "rvn_test_best_overlap": (_i32, [_vp, _u64, _vp, _u32, _u32, _dbl, _vp, _u32, _vp, _vp, _u32]),
+    "rvn_test_second_pass": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _u32, _vp, _u32, _vp]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1554,6 +1555,11 @@ def test_best_overlap(overlaps, read_off, first, err_thr, id_to_target, best, be
     return b, bt
 
 
+class _Pass2Batch(C.Structure):  # rvn_test_pass2_batch (include/raven_hip_test.h)
+    _fields_ = [("q_first", C.c_uint32), ("q_last", C.c_uint32), ("q_origins", C.c_void_p), ("q_read_off", C.c_void_p),
+                ("filtered", C.c_void_p), ("n_query", C.c_uint64), ("overlaps", C.c_void_p), ("n_overlaps", C.c_uint64)]
+
+
 class HookEngine:
     """TEST INFRASTRUCTURE: an engine made by libraven_hip_test.so (a handle belongs to the library that made it), with
     what rvn_test_match_probe needs around it: an index from a crafted stream, the occurrence, the probe itself."""
@@ -1599,6 +1605,52 @@ class HookEngine:
         ms, la = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint64)
         _test_check(T.rvn_engine_kernel_ms(self._h, _p(ms), _p(la), n))
         return {T.rvn_engine_kernel_site_name(i).decode(): int(la[i]) for i in range(n)}
+
+    def upload(self, rs):
+        """A read set of this engine's library (rvn_reads_upload): the handle, to be given back with reads_destroy()."""
+        h = C.c_void_p()
+        packed = np.ascontiguousarray(rs.packed, dtype=np.uint64)
+        _test_check(test_lib().rvn_reads_upload(self._h, _p(packed), int(rs.word_offsets[-1]),
+                                                _p(np.ascontiguousarray(rs.word_offsets, dtype=np.uint64)),
+                                                _p(np.ascontiguousarray(rs.lengths, dtype=np.uint32)),
+                                                _p(np.ascontiguousarray(rs.ids, dtype=np.uint32)), rs.n, C.byref(h)))
+        return h
+
+    def reads_destroy(self, h):
+        test_lib().rvn_reads_destroy(h)
+
+    def second_pass(self, reads_handle, n, pile_begin, pile_end, pile_invalid, identity, kmer_len, batches):
+        """rvn_test_second_pass: the second pass with Map's output of every batch given by the host.  batches = list of
+        (q_first, q_last, origins uint64, read_off uint32[q_last - q_first + 1], filtered uint8, overlaps).  Returns
+        dict(overlaps, contained, kmers, kmers_offsets) as rvn_pass2_fetch fills them."""
+        T = test_lib()
+        keep, arr = [], (_Pass2Batch * max(len(batches), 1))()
+        for i, (qf, ql, org, off, flt, ovl) in enumerate(batches):
+            org = np.ascontiguousarray(org, dtype=np.uint64)
+            off = np.ascontiguousarray(off, dtype=np.uint32)
+            flt = np.ascontiguousarray(flt, dtype=np.uint8)
+            ovl = np.ascontiguousarray(ovl, dtype=OVERLAP_DTYPE)
+            assert off.shape[0] == ql - qf + 1 and flt.shape == org.shape
+            keep.append((org, off, flt, ovl))
+            arr[i] = _Pass2Batch(qf, ql, _p(org) if org.shape[0] else None, _p(off), _p(flt) if flt.shape[0] else None,
+                                 org.shape[0], _p(ovl) if ovl.shape[0] else None, ovl.shape[0])
+        b = np.ascontiguousarray(pile_begin, dtype=np.uint32)
+        en = np.ascontiguousarray(pile_end, dtype=np.uint32)
+        inv = np.ascontiguousarray(pile_invalid, dtype=np.uint8)
+        assert b.shape[0] == n and en.shape[0] == n and inv.shape[0] == n
+        h = C.c_void_p()
+        _test_check(T.rvn_test_second_pass(self._h, reads_handle, _p(b), _p(en), _p(inv), float(identity), int(kmer_len),
+                                           C.cast(arr, C.c_void_p), len(batches), C.byref(h)))
+        try:
+            no, nk = int(T.rvn_pass2_num_overlaps(h)), int(T.rvn_pass2_kmer_cells(h))
+            ovl = np.zeros(no, dtype=OVERLAP_DTYPE)
+            contained = np.zeros(n, dtype=np.uint8)
+            kmers = np.zeros(nk, dtype=np.uint8)
+            koff = np.zeros(n + 1, dtype=np.uint64)
+            _test_check(T.rvn_pass2_fetch(h, _p(ovl), _p(contained), _p(kmers), _p(koff)))
+        finally:
+            T.rvn_pass2_destroy(h)
+        return dict(overlaps=ovl, contained=contained, kmers=kmers, kmers_offsets=koff)
 
     def match_probe(self, q_values, q_origins, q_read_off, avoid_equal, avoid_symmetric):
         """rvn_test_match_probe: (group words, position words, seg_off[n_reads + 1], filtered[n_query])."""
