@@ -1,7 +1,7 @@
 // repeats.h — raven::Pile::FindRepetitiveRegions(median) (RavenLib/src/pile.cc:230-317) and the per-overlap halves of
 // Pile::UpdateRepetitiveRegions / CheckRepetitiveRegions (pile.cc:319-369) as __host__ __device__ code: the pieces of
 // ResolveRepeatInducedOverlaps (construct.cc:493-559) that repeats.hip runs per pile and per overlap, and the same
-// function behind rvn_test_find_repetitive_regions on the CPU.
+// functions that tests/host/repeats_pile.cpp compiles for the host and runs through the whole loop on the CPU.
 //
 // FindRepetitiveRegions appends, in this order, (a) the groups of more than 12 k-mer cells at most 29 cells apart
 // (kmers_), (b) for every up slope i and every later down slope j of FindSlopes(1.42) whose span is a coverage plateau
