@@ -172,6 +172,14 @@ typedef struct rvn_test_pass2_batch {
 int rvn_test_second_pass(rvn_engine* h, const rvn_reads* reads, const uint32_t* pile_begin, const uint32_t* pile_end,
                          const uint8_t* pile_invalid, double identity, uint32_t kmer_len,
                          const rvn_test_pass2_batch* batches, uint32_t n_batches, rvn_pass2** out);
+/* rvn_align_path_batch (the same function: arguments, errors and the result handle, for rvn_paths_info / _fetch /
+ * _fetch_ops / _destroy of THIS library) that also reports what the stage decided and counted.  plans[5 * n_pairs]: per
+ * pair the job's final plan {k, kcap, R, G, S} (threshold of its last attempt, the largest its variant holds, blocks per
+ * lane, lanes per alignment, stripe lanes or 0; all 0 for a pair that was never planned: an empty span).  stats[6]:
+ * {n_aligned, n_retries, n_unaligned, n_batches, band_cells, store_bytes} of the call's NwStats.  With RVN_NW_RATE set in
+ * the environment (this library reads it at every call) the thresholds come from that rate at any batch size. */
+int rvn_test_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                              uint32_t n_pairs, rvn_paths** out, uint32_t* plans, uint64_t* stats);
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n);
 void rvn_test_heap_sort_lendesc(uint64_t* data, uint64_t n);
 

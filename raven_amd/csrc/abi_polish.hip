@@ -4,6 +4,9 @@
 #include <cstring>
 
 #include "abi.h"
+#ifdef RVN_TEST_HOOKS
+#include "../../include/raven_hip_test.h"
+#endif
 #include "nwpath.h"
 #include "poa.h"
 
@@ -132,8 +135,9 @@ int rvn_polish_round(rvn_engine* h, rvn_reads* targets, rvn_reads* reads, const 
                                 ~0ULL, out_codes, out_offsets, out_len, ratio, nullptr, nullptr, stats);
 }
 
-int rvn_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
-                         uint32_t n_pairs, rvn_paths** out) {
+// rvn_align_path_batch; jobs_after (the test hook): the job records as the stage left them, every job's final plan
+static int align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                            uint32_t n_pairs, rvn_paths** out, std::vector<NwJob>* jobs_after) {
   return guarded(h, h && queries && targets && out && (pairs || !n_pairs), "[raven_hip] rvn_align_path_batch: NULL argument",
                  [&](Engine& e) -> int {
     static_assert(sizeof(rvn_align_pair) == 32, "pair layout");
@@ -167,10 +171,35 @@ int rvn_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_read
     res->e = &e;
     res->engine_life = e.life;
     nw_align_paths(e, T, Q, jobs, res->p);
+    if (jobs_after) jobs_after->swap(jobs);
     *out = res.release();
     return RVN_OK;
   });
 }
+
+int rvn_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                         uint32_t n_pairs, rvn_paths** out) {
+  return align_path_batch(h, queries, targets, pairs, n_pairs, out, nullptr);
+}
+
+#ifdef RVN_TEST_HOOKS
+int rvn_test_align_path_batch(rvn_engine* h, const rvn_reads* queries, const rvn_reads* targets, const rvn_align_pair* pairs,
+                              uint32_t n_pairs, rvn_paths** out, uint32_t* plans, uint64_t* stats) {
+  if (!plans || !stats) return fail(RVN_EINVAL, "[raven_hip] rvn_test_align_path_batch: NULL argument");
+  std::vector<NwJob> jobs;
+  const int r = align_path_batch(h, queries, targets, pairs, n_pairs, out, &jobs);
+  if (r != RVN_OK) return r;
+  for (size_t i = 0; i < jobs.size(); ++i) {
+    const NwJob& J = jobs[i];
+    const u32 plan[5] = {J.k, J.kcap, J.R, J.G, J.S};
+    std::memcpy(plans + 5 * i, plan, sizeof(plan));
+  }
+  const NwStats& st = h->e.nw.last;
+  const u64 counted[6] = {st.n_aligned, st.n_retries, st.n_unaligned, st.n_batches, st.band_cells, st.store_bytes};
+  std::memcpy(stats, counted, sizeof(counted));
+  return RVN_OK;
+}
+#endif
 
 int rvn_paths_info(const rvn_paths* p, uint32_t* n_pairs, uint64_t* n_runs, uint64_t* n_ops, uint32_t* n_not_aligned) {
   if (!p) return fail(RVN_EINVAL, "[raven_hip] rvn_paths_info: NULL handle");

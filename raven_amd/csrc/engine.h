@@ -297,6 +297,11 @@ struct PolishStats {
 };
 
 // alignment-path stage (nwpath.hip)
+struct NwStats {
+  u64 n_aligned = 0, n_retries = 0, n_unaligned = 0, n_batches = 0;
+  u64 band_cells = 0, sum_distance = 0, store_bytes = 0;
+  double ms = 0;
+};
 struct NwState {
   struct Set {
     DevBuf hs, ck;  // stored band words (horizontal-delta streams), checkpoints
@@ -304,6 +309,7 @@ struct NwState {
   DevBuf strip, jobs, res;
   double rate = -1.0;  // running estimate of edit distance / length of the read-to-target alignments (< 0: unknown); learned,
                        // not a description of a buffer: it survives release()
+  NwStats last;        // what the last call of nw_breakpoints counted (read by the test hooks only)
   // created together on the first use (open), destroyed with the engine
   hipStream_t streams[5] = {};  // [0..3] walk streams (beside the sweeps), one per buffer set; [4] uploads of a pass planned while another one sweeps
   hipEvent_t ev[5] = {};        // [0..3] the walk of a buffer set is done, [4] sweep -> walk
@@ -320,11 +326,6 @@ struct NwState {
 };
 struct NwJob;
 struct NwWindowRec;
-struct NwStats {
-  u64 n_aligned = 0, n_retries = 0, n_unaligned = 0, n_batches = 0;
-  u64 band_cells = 0, sum_distance = 0, store_bytes = 0;
-  double ms = 0;
-};
 // the path form's slots (nwpath.hip): the blocks the walks wrote their runs into, per job where its runs end
 struct NwPathSlots {
   std::vector<std::unique_ptr<DevBuf>> blocks;

@@ -754,6 +754,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   if (path) path->slot_end.assign(nj, 0);
   hipStream_t s = e.stream;
   if (n_recs) RVN_HIP(hipMemsetAsync(d_recs, 0xFF, n_recs * sizeof(NwWindowRec), s));
+  e.nw.last = st;
   if (nj == 0) return;
   RVN_HIP(hipEventRecord(e.ev0, s));
   if (!e.nw.streams[0]) e.nw.open();
@@ -829,6 +830,7 @@ void nw_breakpoints(Engine& e, const ReadsDev& T, const ReadsDev& Rd, std::vecto
   float ms = 0;
   RVN_HIP(hipEventElapsedTime(&ms, e.ev0, e.ev1));
   st.ms = ms;
+  e.nw.last = st;
   if (knob("RVN_NW_DEBUG"))
     std::fprintf(stderr, "[raven_hip] nw host: plan %.1f ms, order + chunks %.1f ms, uploads %.1f ms, results %.1f ms\n", pass.h_plan, pass.h_order,
                  pass.h_up, pass.h_res);

@@ -215,6 +215,7 @@ _TEST_SIGNATURES = {
     "rvn_test_engine_scratch_bytes": (_i32, [_vp, _pu64]),
     "rvn_test_best_overlap": (_i32, [_vp, _u64, _vp, _u32, _u32, _dbl, _vp, _u32, _vp, _vp, _u32]),
     "rvn_test_second_pass": (_i32, [_vp, _vp, _vp, _vp, _vp, _dbl, _u32, _vp, _u32, _vp]),
+    "rvn_test_align_path_batch": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp, _vp, _vp]),
     "rvn_test_std_sort_lendesc": (None, [_vp, _u64]),
     "rvn_test_heap_sort_lendesc": (None, [_vp, _u64]),
 }
@@ -1618,6 +1619,51 @@ class HookEngine:
 
     def reads_destroy(self, h):
         test_lib().rvn_reads_destroy(h)
+
+    def upload_codes(self, code_arrays):
+        """A read set of this engine's library from one-byte codes (rvn_reads_upload_codes): the handle, as upload()."""
+        lens = np.array([len(a) for a in code_arrays], dtype=np.uint64)
+        off = np.zeros(len(code_arrays) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=off[1:])
+        flat = np.ascontiguousarray(np.concatenate([np.zeros(0, np.uint8)] + [np.asarray(a, np.uint8) for a in code_arrays]))
+        h = C.c_void_p()
+        _test_check(test_lib().rvn_reads_upload_codes(self._h, _p(flat), _p(off), None, len(code_arrays), C.byref(h)))
+        return h
+
+    def set_option(self, name, value):
+        """rvn_engine_set_option (Engine.set_option); returns the previous value."""
+        prev = C.c_int64(0)
+        _test_check(test_lib().rvn_engine_set_option(self._h, name.encode(), int(value), C.byref(prev)))
+        return int(prev.value)
+
+    def align_paths(self, queries, targets, pairs, ops=False, guard=0):
+        """rvn_test_align_path_batch on read handles of this engine: Engine.align_paths' (distances, offsets, runs or ops,
+        pairs not aligned) + plans uint32[n, 5] = every job's final (k, kcap, R, G, S) + the call's counters as a dict.
+        guard > 0: the fetch buffers are that many elements longer, pre-set to a pattern, and come back whole (the caller
+        checks that nothing was written behind the last element)."""
+        pairs = np.ascontiguousarray(pairs, dtype=ALIGN_PAIR_DTYPE)
+        T = test_lib()
+        h = C.c_void_p()
+        plans = np.zeros((max(pairs.shape[0], 1), 5), dtype=np.uint32)
+        stats = np.zeros(6, dtype=np.uint64)
+        _test_check(T.rvn_test_align_path_batch(self._h, queries, targets, _p(pairs), pairs.shape[0], C.byref(h), _p(plans),
+                                                _p(stats)))
+        try:
+            n, n_runs, n_ops, n_bad = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+            _test_check(T.rvn_paths_info(h, C.byref(n), C.byref(n_runs), C.byref(n_ops), C.byref(n_bad)))
+            dist = np.zeros(n.value, dtype=np.uint32)
+            off = np.full(n.value + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+            if ops:
+                out = np.full(n_ops.value + guard, 0xA5, dtype=np.uint8)
+                _test_check(T.rvn_paths_fetch(h, _p(dist), None, None))
+                _test_check(T.rvn_paths_fetch_ops(h, _p(off), _p(out) if n_ops.value else None))
+            else:
+                out = np.full(n_runs.value + guard, 0xA5A5A5A5, dtype=np.uint32)
+                _test_check(T.rvn_paths_fetch(h, _p(dist), _p(off), _p(out) if n_runs.value else None))
+        finally:
+            T.rvn_paths_destroy(h)
+        names = ("n_aligned", "n_retries", "n_unaligned", "n_batches", "band_cells", "store_bytes")
+        return dist, off, out, int(n_bad.value), plans[:pairs.shape[0]], dict(zip(names, (int(x) for x in stats)))
 
     def second_pass(self, reads_handle, n, pile_begin, pile_end, pile_invalid, identity, kmer_len, batches):
         """rvn_test_second_pass: the second pass with Map's output of every batch given by the host.  batches = list of
