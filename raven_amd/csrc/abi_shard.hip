@@ -283,13 +283,10 @@ int shard_chain(rvn_engine* h, const rvn_reads* own, const uint64_t* grp, const 
     if (H && (!grp || !pos)) return fail(RVN_EINVAL, what + ": NULL matches");
     u64* d_seg = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
     put(e, d_seg, seg_off, (static_cast<size_t>(nr) + 1) * 8, kind);
-    u64* g0 = e.map.m_grp[0].get<u64>(H + 1);
-    u64* p0 = e.map.m_pos[0].get<u64>(H + 1);
-    e.map.m_grp[1].reserve((H + 1) * 8);
-    e.map.m_pos[1].reserve((H + 1) * 8);
+    e.map.reserve_matches(H);
     if (H) {
-      put(e, g0, grp, H * 8, kind);
-      put(e, p0, pos, H * 8, kind);
+      put(e, e.map.m_grp[0].as<u64>(), grp, H * 8, kind);
+      put(e, e.map.m_pos[0].as<u64>(), pos, H * 8, kind);
     }
     MapOut& out = e.map.out;
     out.first = 0;

@@ -199,11 +199,16 @@ struct SketchState {
     query_ready = {};
   }
 };
-// Map (map.hip): the last result and the scratch of the match / chain stages
+// Map (map.hip, chain.hip): the last result and the scratch of the match / chain stages
 struct MapState {
   MapOut out;
   DevBuf q_start, q_cnt, m_off;
   DevBuf m_grp[2], m_pos[2];
+  // room for H matches (group and position words): side [0] holds them, side [1] is the chain stage's ping-pong
+  void reserve_matches(u64 H) {
+    m_grp[0].reserve((H + 1) * 8), m_pos[0].reserve((H + 1) * 8);
+    m_grp[1].reserve((H + 1) * 8), m_pos[1].reserve((H + 1) * 8);
+  }
   DevBuf seg_off, iv_slot_begin, iv_slot_end, iv_cnt, iv_off, iv_begin, iv_end;
   DevBuf lis_min, lis_pred, lis_tail, lis_mask, ovl_slots, ovl_flags, ovl_scan, chain_big;
   DevBuf anc_slot_off, anc_slot_cnt;
@@ -241,13 +246,17 @@ void index_filter(Engine& e, double freq);               // sets e.sketch.index.
 void index_key_histogram(Engine& e, std::vector<u64>& hist, std::vector<u32>& over);  // count-of-counts (65536 bins)
 void map_batch(Engine& e, const ReadsDev& r, u32 first, u32 last, bool avoid_equal, bool avoid_symmetric,
                bool minhash, bool want_filtered, MapOut& out);
-
-// self-join of the index for global query ids 0..n_reads-1 -> e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (map.hip)
+// Map() of reads whose own minimizers sit in the index as query-only entries: the polishing round's mapping (map.hip)
 void map_batch_query_only(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 n_query, MapOut& out);
+// self-join of the index for global query ids 0..n_reads-1 -> e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (map.hip)
 u64 join_index_matches(Engine& e, u32 n_reads, bool avoid_equal, bool avoid_symmetric, u32 q_lo = 0,
                        u32 q_hi = 0xFFFFFFFFu);  // only query reads with q_lo <= id < q_hi
-// chain stage of Map on matches already in e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (map.hip)
+// the probe branch of the match stage on a query sketch of nr reads -> the same three buffers; returns the matches (map.hip)
+u64 match_probe(Engine& e, const Sketch& qs, u32 nr, bool avoid_equal, bool avoid_symmetric, u8* filt, u64* seg_off);
+// chain stage of Map on matches already in e.map.m_grp[0] / e.map.m_pos[0] / e.map.seg_off (chain.hip)
 void chain_matches(Engine& e, const ReadsDev& r, u32 first, u32 last, u64 H, MapOut& out);
+// its kernels' opt-in to more than 64 KB of dynamic LDS on the current device: once per engine, where it is created
+void chain_allow_big_lds();
 
 struct EditDistanceState {
   DevBuf cnt, sort, todo;

@@ -192,6 +192,7 @@ int rvn_engine_create(rvn_engine** out, uint32_t k, uint32_t w, uint32_t bandwid
       return fail(RVN_EINVAL, "[raven_hip] window length must be in [1, 256]");
     if (chain == 0) return fail(RVN_EINVAL, "[raven_hip] chain must be >= 1");
     RVN_HIP(hipSetDevice(device));
+    chain_allow_big_lds();
     std::unique_ptr<rvn_engine> h(new rvn_engine());
     Engine& e = h->e;
     e.k = std::min(std::max(k, 1u), 31u);  // as ram's constructor

@@ -81,9 +81,80 @@ int exclusive_scan_host(Engine& e, const uint64_t* in, uint64_t* out, u64 n, u32
   return RVN_OK;
 }
 
+// rvn_test_match_probe (include/raven_hip_test.h): match_probe (map.hip) on a query sketch given by the host.  Every
+// argument that a kernel would index with is checked here; no kernel is launched from here.
+int test_match_probe(Engine& e, const u64* q_values, const u64* q_origins, u64 nq, const u32* q_read_off, u32 nr,
+                     bool avoid_equal, bool avoid_symmetric, u64** grp, u64** pos, u64* seg_off, u8* filtered, u64* n_matches) {
+  *grp = *pos = nullptr;
+  *n_matches = 0;
+  std::memset(seg_off, 0, (static_cast<size_t>(nr) + 1) * 8);
+  if (nq) std::memset(filtered, 0, nq);
+  if (nq >= (1ULL << 32)) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: >= 2^32 query minimizers");
+  if (q_read_off[0] != 0 || q_read_off[nr] != nq) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: offsets must run from 0 to n_query");
+  for (u32 i = 0; i < nr; ++i)
+    if (q_read_off[i + 1] < q_read_off[i]) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: offsets must ascend");
+  const u64 limit = 1ULL << (2 * e.k);  // (k <= 31)
+  for (u64 i = 0; i < nq; ++i)
+    if (q_values[i] >= limit) throw std::invalid_argument("[raven_hip] rvn_test_match_probe: value of more than 2k bits");
+  auto empty = [](u64** p) {
+    *p = static_cast<u64*>(std::malloc(8));
+    if (!*p) throw std::bad_alloc();
+  };
+  if (nq == 0 || e.sketch.index.m == 0) {  // (map_batch returns before the match stage)
+    empty(grp);
+    empty(pos);
+    return RVN_OK;
+  }
+  Sketch& qs = e.sketch.query_sketch;
+  e.sketch.query_ready = {};
+  qs.first = 0;
+  qs.last = nr;
+  qs.count = nq;
+  if (e.val64) {
+    RVN_HIP(hipMemcpy(qs.val.get<u64>(nq + 1), q_values, nq * 8, hipMemcpyHostToDevice));
+  } else {
+    std::vector<u32> v32(nq);
+    for (u64 i = 0; i < nq; ++i) v32[i] = static_cast<u32>(q_values[i]);
+    RVN_HIP(hipMemcpy(qs.val.get<u32>(nq + 1), v32.data(), nq * 4, hipMemcpyHostToDevice));
+  }
+  RVN_HIP(hipMemcpy(qs.org.get<u64>(nq + 1), q_origins, nq * 8, hipMemcpyHostToDevice));
+  RVN_HIP(hipMemcpy(qs.read_off.get<u32>(static_cast<size_t>(nr) + 1), q_read_off, (static_cast<size_t>(nr) + 1) * 4, hipMemcpyHostToDevice));
+  u8* d_filt = e.map.out.filtered.get<u8>(nq + 1);
+  u64* d_seg = e.map.seg_off.get<u64>(static_cast<size_t>(nr) + 2);
+  const u64 H = match_probe(e, qs, nr, avoid_equal, avoid_symmetric, d_filt, d_seg);
+  RVN_HIP(hipMemcpy(filtered, d_filt, nq, hipMemcpyDeviceToHost));
+  *grp = static_cast<u64*>(std::malloc((H + 1) * 8));
+  *pos = static_cast<u64*>(std::malloc((H + 1) * 8));
+  if (!*grp || !*pos) throw std::bad_alloc();
+  if (H) {
+    RVN_HIP(hipMemcpy(*grp, e.map.m_grp[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(*pos, e.map.m_pos[0].ptr, H * 8, hipMemcpyDeviceToHost));
+    RVN_HIP(hipMemcpy(seg_off, d_seg, (static_cast<size_t>(nr) + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  *n_matches = H;
+  return RVN_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rvn_test_match_probe(rvn_engine* h, const uint64_t* q_values, const uint64_t* q_origins, uint64_t n_query,
+                         const uint32_t* q_read_off, uint32_t n_reads, int avoid_equal, int avoid_symmetric,
+                         uint64_t** group, uint64_t** positions, uint64_t* seg_off, uint8_t* filtered, uint64_t* n_matches) {
+  const bool ok = h && q_read_off && group && positions && seg_off && n_matches && !(n_query && (!q_values || !q_origins || !filtered));
+  return guarded(h, ok, "[raven_hip] rvn_test_match_probe: NULL argument", [&](Engine& e) -> int {
+    try {
+      return test_match_probe(e, q_values, q_origins, n_query, q_read_off, n_reads, avoid_equal != 0, avoid_symmetric != 0, group,
+                              positions, seg_off, filtered, n_matches);
+    } catch (...) {
+      std::free(*group);
+      std::free(*positions);
+      *group = *positions = nullptr;
+      throw;
+    }
+  });
+}
 
 int64_t rvn_test_find_chimeric_regions(const uint16_t* data, uint32_t size, uint32_t* out, uint64_t cap_pairs) {
   if (!data || !out || size == 0) return RVN_EINVAL;

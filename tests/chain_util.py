@@ -1,4 +1,4 @@
-"""Crafted match lists for the chain stage of Map (raven_amd/csrc/map.hip: chain_matches) and a second, plain-Python
+"""Crafted match lists for the chain stage of Map (raven_amd/csrc/chain.hip: chain_matches) and a second, plain-Python
 statement of ram's MinimizerEngine::Chain to hold the C++ oracle to on the same lists.
 
 Encoding (ram's Match):  group = (rhs_id << 1 | strand) << 32 | diagonal,  positions = lhs_pos << 32 | rhs_pos.
@@ -18,9 +18,10 @@ import numpy as np
 M32 = 0xFFFFFFFF
 U = np.uint64
 
-# The size classes of map.hip, restated (kSegClassCap, kChainSmallCap, kChainClassCap): a read's group sort runs in LDS
-# up to 4096 matches and as a wave sort beyond ("big"); an interval of <= 32 matches is chained by one lane, larger ones
-# by one wave out of LDS up to 8192 matches and out of global scratch beyond ("global").
+# The size classes of raven_amd/csrc/sizeclass.h, restated (kSegClassTable, kChainSmallCap, kChainClassTable;
+# tests/test_size_class.py holds the two to each other): a read's group sort runs in LDS up to 4096 matches and
+# as a wave sort beyond ("big"); an interval of <= 32 matches is chained by one lane, larger ones by one wave
+# out of LDS up to 8192 matches and out of global scratch beyond ("global").
 SEG_CLASS_CAPS = (256, 512, 1024, 2048, 4096)
 CHAIN_SMALL_CAP = 32
 CHAIN_CLASS_CAPS = (128, 256, 512, 768, 1024, 2048, 4096, 8192)

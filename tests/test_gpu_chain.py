@@ -1,4 +1,4 @@
-"""GPU: the chain stage of Map (raven_amd/csrc/map.hip: chain_matches — group sort, diagonal bands, position sort,
+"""GPU: the chain stage of Map (raven_amd/csrc/chain.hip: chain_matches — group sort, diagonal bands, position sort,
 chain_small_kernel / chain_wave, emission, overlap slots) against ram's Chain on crafted match lists.
 
 Every test feeds host match lists to Engine.shard_chain (rvn_shard_chain runs exactly chain_matches; the reads give only
@@ -77,9 +77,9 @@ def _check(engines, k, params, built):
 
 
 def test_every_size_class_in_one_call(engines):
-    """One batch, one call, and the launch counts say that every class ran: the class tables of map.hip restated —
-    group sort of a read (kSegClassCap): LDS for <= 256 / 512 / 1024 / 2048 / 4096 matches + the wave sort beyond = 6;
-    position sort and chain of an interval above 32 matches (kChainClassCap): LDS for <= 128 / 256 / 512 / 768 / 1024 /
+    """One batch, one call, and the launch counts say that every class ran: the class tables of sizeclass.h restated —
+    group sort of a read (kSegClassTable): LDS for <= 256 / 512 / 1024 / 2048 / 4096 matches + the wave sort beyond = 6;
+    position sort and chain of an interval above 32 matches (kChainClassTable): LDS for <= 128 / 256 / 512 / 768 / 1024 /
     2048 / 4096 / 8192 + global scratch beyond = 9 each; chain_small (<= kChainSmallCap = 32): one launch."""
     he, _ = engines(15, cu.DEFAULT_PARAMS)
     b, _ = cu.class_batch()
