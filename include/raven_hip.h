@@ -728,6 +728,38 @@ int rvn_unitigs_as_reads(rvn_engine* e, const rvn_unitigs* u, const rvn_tiling* 
 int rvn_tiling_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* reads, const uint32_t* nodes, uint32_t n,
                         rvn_reads** out);
 
+/* The similarity test of raven's RemoveBubbles (RavenLib/src/assemble.cc:225-281) without a base on the
+ * host: the sequences of node PATHS as a device read set, and the reference's verdict on pairs of them.
+ *
+ * rvn_tiling_paths_as_reads: path p has the members path_node[path_offsets[p] .. path_offsets[p + 1]).  Its sequence is,
+ * for every member but the last, the first min(path_label[i], length(node)) bases of the node (Edge::Label() as
+ * biosoup::NucleicAcid::InflateData(0, length) returns it: a length beyond the sequence gives the whole sequence, so an
+ * edge length that has wrapped in 32 bits is NOT refused here; label 0 contributes nothing), then the whole last node,
+ * whose label is ignored.  The result is a read set like any other (ids 0 .. n_paths - 1), equal to
+ * rvn_reads_upload_codes of the same strings word for word.  The paths' tilings are temporary: the tiling is not changed.
+ * RVN_EINVAL (the message names the offender): a node that is not in the tiling, a read set other than the tiling's, an
+ * empty path, offsets that decrease, a path of 2^32 bases or more.  n_paths == 0 gives an empty read set.
+ *
+ * rvn_path_similarity_batch: `paths` is such a read set (or any other), a pair names two of its reads.  With l, r the
+ * two lengths and mx = max(l, r), similar[i] = 1 exactly when the reference goes on to pop the bubble:
+ *   !(min(l, r) < mx * min_ratio)      (the product formed in double, assemble.cc:267)  and
+ *   !(1 - d / (double)mx < min_ratio)  with d the exact global unit-cost edit distance (edlibAlign, default configuration).
+ * The second rule is decided by a bounded sweep per pair at kmax = the largest x that still passes it (one sweep where the
+ * wave ring of the edit-distance stage holds kmax); pairs the length rule rejects are never swept.  distance (may be NULL): the exact distance where it is <= kmax, 0xFFFFFFFE where it is
+ * above, 0xFFFFFFFF for a pair rejected by the length rule.  min_ratio is the reference's 0.8.  A threshold beyond the
+ * wave ring (8 064: paths of 40 kb and more at 0.8) is swept by a ring over the lanes of one workgroup (engine option
+ * ed_wide_lanes; up to 65 408; one sweep, at kmax or at the ring's capacity), what lies beyond that by the full sweep:
+ * exact at any size.
+ * RVN_EINVAL: a pair that names an unknown read, a path of length 0 (the reference's arithmetic on it is 0 / 0), a
+ * min_ratio that is not a number.  Every pair is checked first: a refused call has written nothing. */
+typedef struct rvn_path_pair {
+  uint32_t lhs_path, rhs_path;
+} rvn_path_pair;
+int rvn_tiling_paths_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* reads, uint32_t n_paths,
+                              const uint64_t* path_offsets, const uint32_t* path_node, const uint32_t* path_label, rvn_reads** out);
+int rvn_path_similarity_batch(rvn_engine* e, const rvn_reads* paths, const rvn_path_pair* pairs, uint32_t n_pairs, double min_ratio,
+                              uint8_t* similar, uint32_t* distance);
+
 /* Tuning a deployment may set; -1 restores the built-in default of any option (so does 0, except for poa_rows_min_windows).
  * No option changes an overlap list, a pile or a layer table; poa_rows_min_windows chooses which window-consensus kernel
  * makes the first attempt, and the two agree on 19 998 of 20 000 C4-like windows, not on every one: a
@@ -742,6 +774,10 @@ int rvn_tiling_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* rea
  *   nw_stripe_lanes    alignment-path stage: the widest ring of one sweep, in lanes (1 .. 64; default 64, a whole wave).  A band
  *                      wider than that ring is swept in stripes of that many lanes (at most 8 rings: 262 144 rows by default);
  *                      smaller values force striping on small inputs; same records either way
+ *   ed_wide_lanes      rvn_path_similarity_batch: lanes of the workgroup ring that sweeps thresholds beyond the wave ring (64 .. 512
+ *                      in steps of 64; default 512 = thresholds up to 65 408); 1 = no such sweep, those pairs take the usual
+ *                      route to the full sweep; smaller rings reach their limit on small inputs; same verdicts and distances
+ *                      either way.  Any other value is refused
  *   index_direct_min_keys  index: distinct values from which all 4^k possible values are addressed directly (an 8-GB table at
  *                      k = 15, one cache line per probe; default 8 388 608; 1 = every index with k <= 15); same matches either way
  *   poa_rows_min_windows  window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (default 8 192;
@@ -754,7 +790,8 @@ int rvn_tiling_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* rea
  *   polish_join        != 0: a round maps by sorting the reads' minimizers with the targets' and streaming the runs instead of
  *                      probing the targets' index — same overlaps, slower at the metric's size
  * previous (may be NULL) receives the value the option had (its default's value when it was at the default).  RVN_EINVAL:
- * unknown name, a value below -1, io_ring == 1 (a ring needs two slabs). */
+ * unknown name, a value below -1, io_ring == 1 (a ring needs two slabs), an ed_wide_lanes that is neither 1 nor a multiple of
+ * 64 from 64 to 512. */
 int rvn_engine_set_option(rvn_engine* e, const char* name, int64_t value, int64_t* previous);
 
 /* Kept for source compatibility: a round no longer has a host cutting stage to overlap with the POA, all windows

@@ -1,6 +1,7 @@
 // abi_graph.hip — C ABI (include/raven_hip.h): the assembly graph on the device (graph.hip): rvn_construct_assembly_graph,
 // rvn_graph_from_edges, the marking of transitive and long edges, and what a graph handle gives back; node sequences as
-// tilings, rvn_graph_create_unitigs and unitig sequences as read sets (unitigs.hip).
+// tilings, rvn_graph_create_unitigs and unitig sequences as read sets (unitigs.hip); node paths as read sets and
+// RemoveBubbles' similarity verdict on pairs of them (unitigs.hip, edit_distance.hip).
 #include <cmath>
 #include <cstring>
 
@@ -284,6 +285,29 @@ int rvn_tiling_as_reads(rvn_engine* h, const rvn_tiling* t, const rvn_reads* rea
     *out = nullptr;
     if (t->device != e.device) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_as_reads: the tiling lives on another device");
     return nodes_as_reads(e, t, reads, std::vector<u32>(nodes, nodes + n), out);
+  });
+}
+
+int rvn_tiling_paths_as_reads(rvn_engine* h, const rvn_tiling* t, const rvn_reads* reads, uint32_t n_paths, const uint64_t* path_offsets,
+                              const uint32_t* path_node, const uint32_t* path_label, rvn_reads** out) {
+  const bool args_ok = h && t && reads && out && (n_paths == 0 || (path_offsets && path_node && path_label));
+  return guarded(h, args_ok, "[raven_hip] rvn_tiling_paths_as_reads: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (t->device != e.device) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_paths_as_reads: the tiling lives on another device");
+    std::unique_ptr<rvn_reads> rr(new rvn_reads());
+    tiling_paths_as_reads(e, t->t, reads->r, n_paths, path_offsets, path_node, path_label, rr->r);
+    *out = rr.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_path_similarity_batch(rvn_engine* h, const rvn_reads* paths, const rvn_path_pair* pairs, uint32_t n_pairs, double min_ratio,
+                              uint8_t* similar, uint32_t* distance) {
+  const bool args_ok = h && paths && (n_pairs == 0 || (pairs && similar));
+  return guarded(h, args_ok, "[raven_hip] rvn_path_similarity_batch: NULL argument", [&](Engine& e) -> int {
+    static_assert(sizeof(rvn_path_pair) == 8, "a pair is two read indices");
+    path_similarity_batch(e, paths->r, reinterpret_cast<const u32*>(pairs), n_pairs, min_ratio, similar, distance);
+    return RVN_OK;
   });
 }
 

@@ -18,9 +18,13 @@
 // Integer VALU bound (no MFMA, negligible HBM): report cell updates/s.
 #include <algorithm>
 #include <cstring>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "engine.h"
 #include "myers.h"
+#include "overlap_rules.h"
 #include "wave.h"
 #ifdef RVN_TEST_HOOKS
 #include "../../include/raven_hip_test.h"
@@ -176,6 +180,137 @@ __global__ __launch_bounds__(256) void ed_banded_kernel(const u64* __restrict__ 
     }
   }
   if (lane_id() == 0) out[p] = res;
+}
+
+// ---- the same ring over the lanes of a whole WORKGROUP: thresholds beyond the wave ring (path_similarity_batch) ----
+// ed_banded's ring has 64 lanes, so its threshold ends at 32 R 63.  Here the ring is the L = blockDim.x lanes of one
+// workgroup (a multiple of 64, at most kEdWideMaxLanes: eight wave rings by default): lane p holds the super-blocks
+// p, p + L, ..., and the carry to the next lane — the horizontal delta and the bottom score of the step before — goes
+// through LDS instead of a shuffle, double-buffered, with ONE barrier per column step.  Every lane runs every step and
+// meets every barrier; the only dependencies are those barriers and the kernel boundary, no wave waits on anything
+// another workgroup writes.  The cost is (columns + super-blocks) steps of a workgroup instead of the full sweep's
+// (stripes x columns) steps of one wave: for two sequences of 500 000 bases 0.5 M steps against 61 M.
+constexpr int kEdWideMaxLanes = 512;
+template <int R>
+__device__ u32 ed_banded_wide(const u64* __restrict__ a_words, u64 a_base, u32 n, const u64* __restrict__ b_words, u64 b_base, u32 m,
+                              bool rc, long long k, int (*carry)[kEdWideMaxLanes][2], u32* shared_result) {
+  const int L = static_cast<int>(blockDim.x), pos = static_cast<int>(threadIdx.x);
+  const long long nb = (static_cast<long long>(n) + 63) >> 6;
+  const long long n_super = (nb + R - 1) / R;
+  u64 Pv[R], Mv[R], peq[R][4];
+  int score[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) score[r] = 0;
+  long long s = pos;
+  bool fresh = true;
+  TextCursor tc;
+  int hout_last = 1, score_last = 0;
+  u32 result = 0;
+  if (pos == 0) *shared_result = 0;
+  carry[1][pos][0] = 1;  // what "the step before the first" left
+  carry[1][pos][1] = 0;
+  __syncthreads();
+  const int src = pos == 0 ? L - 1 : pos - 1;
+  const long long t_end = static_cast<long long>(m) + n_super;
+  for (long long t = 0; t < t_end; ++t) {
+    const int hin_prev = carry[(t + 1) & 1][src][0];  // written in step t - 1
+    const int score_prev = carry[(t + 1) & 1][src][1];
+    while (s < n_super) {  // retire finished super-blocks (ring advance)
+      const long long last_b = s * R + R - 1 < nb ? s * R + R - 1 : nb - 1;
+      const long long jout = 64 * last_b + 64 + k;
+      if (t - s > (jout < m ? jout : m)) {
+        s += L;
+        fresh = true;
+      } else {
+        break;
+      }
+    }
+    const long long j = t - s;
+    const long long b0 = s * R;
+    const long long jin0 = 64 * b0 - k + 1 < 1 ? 1 : 64 * b0 - k + 1;
+    if (s < n_super && j >= jin0 && j <= m) {
+      if (fresh) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) load_peq(a_words, a_base, n, static_cast<u32>(b0 + r), peq[r]);
+        tc.init(b_words, b_base, m, rc, j);
+        fresh = false;
+      }
+      const unsigned c = tc.get(j);
+      const bool prod_active = b0 > 0 && j <= 64 * b0 + k;
+      int hin = prod_active ? hin_prev : 1;
+      int above_prev_col = prod_active ? score_prev - hin_prev : score_prev;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const long long b = b0 + r;
+        if (b >= nb) break;
+        const long long jin = 64 * b - k + 1 < 1 ? 1 : 64 * b - k + 1;
+        const long long jout = 64 * b + 64 + k;
+        if (j < jin) break;
+        if (j > jout) {
+          hin = 1;
+          continue;
+        }
+        if (j == jin) {
+          Pv[r] = ~0ULL;
+          Mv[r] = 0;
+          score[r] = jin == 1 ? static_cast<int>(64 * (b + 1)) : above_prev_col + 64;
+        }
+        const int old = score[r];
+        const u64 eq = c == 0 ? peq[r][0] : (c == 1 ? peq[r][1] : (c == 2 ? peq[r][2] : peq[r][3]));
+        const int hout = myers_block(Pv[r], Mv[r], eq, hin);
+        score[r] = old + hout;
+        above_prev_col = old;
+        hin = hout;
+        if (b == nb - 1 && j == m) {
+          const u32 used = n - static_cast<u32>(64 * b);
+          const u64 padmask = used >= 64 ? 0ULL : ~((1ULL << used) - 1ULL);
+          result = static_cast<u32>(score[r] - RVN_POPC64(Pv[r] & padmask) + RVN_POPC64(Mv[r] & padmask)) + 1u;
+        }
+      }
+      hout_last = hin;
+      score_last = score[R - 1];
+    }
+    carry[t & 1][pos][0] = hout_last;
+    carry[t & 1][pos][1] = score_last;
+    __syncthreads();
+  }
+  if (result) atomicMax(shared_result, result);  // exactly one lane holds result + 1
+  __syncthreads();
+  const u32 found = *shared_result;
+  __syncthreads();  // (the next sweep resets it)
+  return found - 1u;
+}
+
+// One workgroup per pair (todo == nullptr: pair q is entry q).  A sweep costs (columns + super-blocks) barrier steps of the
+// whole ring whatever its threshold, so a smaller first threshold saves nothing: there is ONE sweep, at kmax where the ring
+// holds it (bounded: that sweep decides) and at the ring's capacity otherwise.  What lies beyond stays kEdOverflow for the
+// full sweep.  Every branch on the way is uniform over the workgroup.
+template <int R>
+__global__ __launch_bounds__(kEdWideMaxLanes) void ed_wide_kernel(const u64* __restrict__ packed, const u64* __restrict__ word_off,
+                                                                 const EdPair* __restrict__ pairs, const u32* __restrict__ todo, u32 n_todo,
+                                                                 const u32* __restrict__ kmax, u32* __restrict__ out) {
+  __shared__ int carry[2][kEdWideMaxLanes][2];
+  __shared__ u32 shared_result;
+  const u32 q = blockIdx.x;
+  if (q >= n_todo) return;
+  const u32 p = todo ? todo[q] : q;
+  const EdPair pr = pairs[p];
+  const u32 n = pr.a_len, m = pr.b_len;
+  const long long km = kmax ? static_cast<long long>(kmax[p]) : (1LL << 40);
+  const long long cap = 32LL * R * (static_cast<long long>(blockDim.x) - 1);
+  const long long d = n > m ? n - m : m - n;
+  u32 res = kEdOverflow;
+  if (n == 0 || m == 0 || d > km) {
+    res = (n == 0 || m == 0) && d <= km ? n + m : kEdAbove;  // the distance is at least the length difference
+  } else if (d <= cap) {
+    const long long k = km < cap ? km : cap;  // (>= d: see above)
+    const u64* aw = packed + word_off[pr.a_idx];
+    const u64* bw = packed + word_off[pr.b_idx];
+    const u32 r = ed_banded_wide<R>(aw, pr.a_begin, n, bw, pr.b_begin, m, pr.strand == 0, k, carry, &shared_result);
+    if (static_cast<long long>(r) <= k) res = r;  // exact, and k <= km
+    else if (k >= km) res = kEdAbove;             // distance > k = threshold
+  }
+  if (threadIdx.x == 0) out[p] = res;
 }
 
 // The text of a lane, 32 columns at a time, fetched at the SAME columns by every lane of the wave (column j with
@@ -557,13 +692,25 @@ extern "C" int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off
 
 // pairs and results resident in HBM: d_pairs = n_pairs x {a_idx,a_begin,a_len,b_idx,b_begin,b_len,strand,0}, d_out u32[n].
 // d_kmax (nullable): per-pair thresholds — distances above them come back as 0xFFFFFFFE (see ed_banded_kernel).
-void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32 n_pairs, u32* d_out, const u32* d_kmax) {
+// wide_sweep: the caller's thresholds lie beyond the wave ring; the pairs go to the workgroup ring (ed_wide_kernel) and from
+// there to the full sweep, not through the lane windows and the wave ring (engine option ed_wide_lanes = 1: the usual route).
+void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32 n_pairs, u32* d_out, const u32* d_kmax, bool wide_sweep) {
   if (n_pairs == 0) return;
   hipStream_t s = e.stream;
   const EdPair* d_pairs = reinterpret_cast<const EdPair*>(d_pairs_raw);
   u32* d_cnt = e.ed.cnt.get<u32>(kEdHistAt + kEdHistBins);
   RVN_HIP(hipMemsetAsync(d_cnt, 0, (kEdHistAt + kEdHistBins) * 4, s));
   RVN_HIP(hipMemsetAsync(d_out, 0xFF, static_cast<size_t>(n_pairs) * 4, s));  // everything starts as "needs the wave kernel"
+  u32* d_todo = e.ed.todo.get<u32>(static_cast<size_t>(n_pairs) + 1);
+  if (wide_sweep && e.opt.ed_wide_lanes != 1) {
+    // ---- the caller's pairs all have thresholds beyond the wave ring: the ring over a workgroup's lanes decides them in one
+    // sweep (the lane windows and the wave ring's eight sweeps in front of it would each cost as many column steps as
+    // the pair is long, and could decide nothing that sweep does not) ----
+    const long long asked = e.opt.ed_wide_lanes;  // (rvn_engine_set_option admits 64 .. 512 in steps of 64)
+    const u32 lanes = asked >= 64 && asked <= kEdWideMaxLanes ? static_cast<u32>(asked) : static_cast<u32>(kEdWideMaxLanes);
+    RVN_KLAUNCH(kKEditWide, ed_wide_kernel<4><<<n_pairs, lanes, 0, s>>>(r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, nullptr, n_pairs,
+                                                                        d_kmax, d_out));
+  } else {
   // ---- stage 1: one lane per pair for narrow bands.  Tried on a sample first: it pays only when most pairs are
   // closer than ~384 edits (HiFi-like); for ONT-like spans nearly every pair would come back as overflow.
   u32* d_sk = e.ed.sort.get<u32>(4 * static_cast<size_t>(n_pairs) + 8);
@@ -622,7 +769,6 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
     for (int c = kEdClasses - 1; c >= 1; --c) piece(h_cnt[kEdBoundsAt + c - 1], class_b[c]);
     piece(n_main, class_b[0]);
   }
-  u32* d_todo = e.ed.todo.get<u32>(static_cast<size_t>(n_pairs) + 1);
   if (narrow_used) {  // second chance with the widest window for the pairs a narrower one lost
     RVN_HIP(hipMemsetAsync(d_cnt, 0, 4, s));
     ed_collect_overflow_kernel<<<div_up(n_pairs, 256), 256, 0, s>>>(d_out, n_pairs, false, d_todo, d_cnt);
@@ -640,6 +786,7 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
   if (n_todo == 0) return;
   RVN_KLAUNCH(kKEditBanded, ed_banded_kernel<4><<<div_up(n_todo, 4), 256, 0, s>>>(
                                 r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, d_todo, n_todo, d_kmax, d_out));
+  }
   // ---- stage 3: pairs beyond the ring capacity (rare): unbanded striped sweep, exact ----
   RVN_HIP(hipMemsetAsync(d_cnt, 0, 4, s));
   ed_collect_overflow_kernel<<<div_up(n_pairs, 256), 256, 0, s>>>(d_out, n_pairs, true, d_todo, d_cnt);
@@ -665,6 +812,61 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
   RVN_KLAUNCH(kKEditFull, ed_full_kernel<<<n_full, 64, 0, s>>>(r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, d_todo, n_full,
                                                                d_off, d_hb, d_out));
   RVN_HIP(rvn_stream_sync(s));  // the host lists above are locals
+}
+
+// RemoveBubbles' similarity test (RavenLib/src/assemble.cc:264-281) on pairs of whole reads of P.  The length rule and the
+// threshold are host arithmetic on the lengths (the reference's doubles: overlap_rules.h); what passes the length rule is
+// swept bounded by its kmax, in two batches: thresholds the wave ring holds take edit_distance_dev's usual route (one sweep
+// at kmax decides), the others its wide route (the workgroup ring, then the full sweep).  The full sweep comes back with
+// an exact distance, which may lie above kmax: the report is made uniform here.  Nothing is written before every pair
+// has been checked.
+void path_similarity_batch(Engine& e, const ReadsDev& P, const u32* h_pairs, u32 n_pairs, double min_ratio, u8* h_similar,
+                           u32* h_distance) {
+  const std::string who = "[raven_hip] rvn_path_similarity_batch: ";
+  if (min_ratio != min_ratio) throw std::invalid_argument(who + "min_ratio is not a number");
+  for (u32 i = 0; i < n_pairs; ++i) {
+    const u32 a = h_pairs[2 * i], b = h_pairs[2 * i + 1];
+    if (a >= P.n || b >= P.n) throw std::invalid_argument(who + "pair " + std::to_string(i) + " names an unknown path");
+    if (P.h_len[a] == 0 || P.h_len[b] == 0)
+      throw std::invalid_argument(who + "path " + std::to_string(P.h_len[a] == 0 ? a : b) + " (pair " + std::to_string(i) + ") has no bases");
+  }
+  constexpr u32 kWaveRing = 32u * 4u * 63u;  // ed_banded_kernel<4>'s capacity
+  struct Batch {
+    std::vector<EdPair> pairs;
+    std::vector<u32> kmax, at;
+  } batch[2];  // [0] thresholds inside the wave ring, [1] beyond it
+  for (u32 i = 0; i < n_pairs; ++i) {
+    const u32 a = h_pairs[2 * i], b = h_pairs[2 * i + 1];
+    const u32 l = P.h_len[a], r = P.h_len[b];
+    const u32 mx = l > r ? l : r, mn = l > r ? r : l;
+    h_similar[i] = 0;
+    if (h_distance) h_distance[i] = kEdOverflow;
+    if (mn < mx * min_ratio) continue;  // (uint32 < uint32 * double, as the reference forms it)
+    const u32 k = identity_kmax(mx, min_ratio);
+    Batch& to = batch[k > kWaveRing ? 1 : 0];
+    to.pairs.push_back(EdPair{a, 0, l, b, 0, r, 1u, 0u});
+    to.kmax.push_back(k);
+    to.at.push_back(i);
+  }
+  hipStream_t s = e.stream;
+  for (int wide = 0; wide < 2; ++wide) {
+    const Batch& B = batch[wide];
+    const u32 n = static_cast<u32>(B.pairs.size());
+    if (n == 0) continue;
+    const EdPair* d_pairs = upload(e.scratch.tmp_a, B.pairs.data(), n, s);
+    const u32* d_kmax = upload(e.scratch.tmp_c, B.kmax.data(), n, s);
+    u32* d_out = e.scratch.tmp_b.get<u32>(static_cast<size_t>(n) + 1);
+    edit_distance_dev(e, P, reinterpret_cast<const u32*>(d_pairs), n, d_out, d_kmax, wide != 0);
+    std::vector<u32> dist(n);
+    RVN_HIP(hipMemcpyAsync(dist.data(), d_out, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, s));
+    RVN_HIP(rvn_stream_sync(s));
+    for (u32 q = 0; q < n; ++q) {
+      const bool within = dist[q] <= B.kmax[q];
+      // kmax = 0 also stands for "no distance passes" (identity_kmax): the rule itself has the last word
+      h_similar[B.at[q]] = within && identity_keeps(dist[q], std::max(B.pairs[q].a_len, B.pairs[q].b_len), min_ratio) ? 1 : 0;
+      if (h_distance) h_distance[B.at[q]] = within ? dist[q] : kEdAbove;
+    }
+  }
 }
 
 // pairs: host array of n_pairs x 8 u32 {a_idx,a_begin,a_len,b_idx,b_begin,b_len,strand,0}; out: host u32[n_pairs]

@@ -127,6 +127,8 @@ struct EngineOptions {
                                      // by the number of alignments in the launch.  Same records either way
   long long nw_stripe_lanes = 0;     // alignment-path stage: lanes of the widest ring of one sweep (1 .. 64, default 64 = a wave); a band
                                      // wider than that is swept in stripes of that many super-blocks (nwpath.h).  Same records either way
+  long long ed_wide_lanes = 0;       // path similarity: lanes of the workgroup ring that sweeps thresholds beyond the wave ring (64 .. 512 in
+                                     // steps of 64, default 512); 1 = no such sweep, those pairs are the full sweep's.  Same distances either way
   long long index_direct_min_keys = 0;  // index: distinct values from which every possible value is addressed directly (index.hip; default 8 M,
                                      // 1 = every index with 2k <= 30 bits — the tests of that path on small inputs).  Same matches either way
   long long poa_rows_min_windows = -1;  // window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (poa4.hip);
@@ -267,7 +269,10 @@ struct EditDistanceState {
 void edit_distance_batch(Engine& e, const ReadsDev& r, const u32* h_pairs, u32 n_pairs, u32* h_out, double* kernel_ms,
                          u64* cells);
 // the same with pairs and distances resident in HBM (pass2.hip: identity filters)
-void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs, u32 n_pairs, u32* d_out, const u32* d_kmax = nullptr);
+// wide_sweep: the pairs' thresholds lie beyond the wave ring; they go straight to the ring over a workgroup's lanes and
+// from there to the full sweep (path_similarity_batch alone asks for it, for that part of its pairs)
+void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs, u32 n_pairs, u32* d_out, const u32* d_kmax = nullptr,
+                       bool wide_sweep = false);
 
 // window consensus (poa.hip): scratch of a batch, which kernels run (tests), and what the last batch / all batches did
 struct PoaState {
@@ -670,7 +675,9 @@ struct UnitigScratch {
   DevBuf indeg, outdeg, in_e, out_e, succ, cls, ptr[2], dist[2], endn[2], mn[2], cyc, flag, slot, cbegin, chain_of_end, chain_len;
   DevBuf count, cov, mcount, moff, members, mnode, mlen, mseg, mcnt, lenscan, segscan, cntscan, mark, err;
   DevBuf ubegin, uend, ucount, ulen, ucov, ucirc, uis, useg, ecnt, eoff, etail, ehead, elen, nodes, woff;
+  DevBuf pseg, pcum, pseg_off, plen;  // the temporary tiling of tiling_paths_as_reads: one node per path
   void for_each_buf(const BufFn& f) {
+    f(pseg), f(pcum), f(pseg_off), f(plen);
     f(indeg), f(outdeg), f(in_e), f(out_e), f(succ), f(cls), f(ptr[0]), f(ptr[1]), f(dist[0]), f(dist[1]), f(endn[0]), f(endn[1]);
     f(mn[0]), f(mn[1]), f(cyc), f(flag), f(slot), f(cbegin), f(chain_of_end), f(chain_len);
     f(count), f(cov), f(mcount), f(moff), f(members), f(mnode), f(mlen), f(mseg), f(mcnt), f(lenscan), f(segscan), f(cntscan), f(mark), f(err);
@@ -689,6 +696,14 @@ void graph_create_unitigs(Engine& e, const GraphDev& g, TilingDev& T, const u32*
                           u32 min_unitig_size, UnitigTables& out);
 // the sequences of the listed nodes of T as a read set over the reads R the tiling was made for (read i = node h_nodes[i])
 void tiling_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, const u32* h_nodes, u32 n, ReadsDev& out);
+// the sequences of node paths (CSR h_off[n_paths + 1] over h_node / h_label) as a read set: per member but the last the
+// first min(label, length) bases, then the whole last node (unitig_rules.h: path_member_keep).  T is not changed
+void tiling_paths_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, u32 n_paths, const u64* h_off, const u32* h_node,
+                           const u32* h_label, ReadsDev& out);
+// RemoveBubbles' verdict on pairs (lhs, rhs) of reads of P (edit_distance.hip): h_pairs = n x 2 read indices; h_distance
+// may be nullptr
+void path_similarity_batch(Engine& e, const ReadsDev& P, const u32* h_pairs, u32 n_pairs, double min_ratio, u8* h_similar,
+                           u32* h_distance);
 // what every device-made read set shares once its packed words lie in r.packed (abi_reads.hip): the tables, the ids, the tiles
 void reads_finish_device_set(Engine& e, ReadsDev& r, const std::vector<u64>& woff, const std::vector<u32>& lens, const uint32_t* ids,
                              u64 total_bases);

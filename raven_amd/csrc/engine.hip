@@ -99,7 +99,7 @@ void fetch_values(Engine& e, const DevBuf& val, u64 n, u64* values) {
 }
 
 const char* engine_option_names() {
-  return "nw_budget_mb, nw_group_walk, nw_stripe_lanes, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
+  return "nw_budget_mb, nw_group_walk, nw_stripe_lanes, ed_wide_lanes, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
          "no_arena, release_always, polish_join, polish_sketch_cache_mb";
 }
 long long* engine_option(EngineOptions& o, const char* name) {
@@ -107,6 +107,7 @@ long long* engine_option(EngineOptions& o, const char* name) {
   if (n == "nw_budget_mb") return &o.nw_budget_mb;
   if (n == "nw_group_walk") return &o.nw_group_walk;
   if (n == "nw_stripe_lanes") return &o.nw_stripe_lanes;
+  if (n == "ed_wide_lanes") return &o.ed_wide_lanes;
   if (n == "index_direct_min_keys") return &o.index_direct_min_keys;
   if (n == "poa_rows_min_windows") return &o.poa_rows_min_windows;
   if (n == "io_threads") return &o.io_threads;
@@ -249,6 +250,8 @@ int rvn_engine_set_option(rvn_engine* h, const char* name, int64_t value, int64_
   const bool is_rows = slot == &h->e.opt.poa_rows_min_windows;
   if (slot == &h->e.opt.io_ring && value == 1)
     return fail(RVN_EINVAL, "[raven_hip] rvn_engine_set_option: io_ring needs at least 2 slabs in flight (0 or -1: the default)");
+  if (slot == &h->e.opt.ed_wide_lanes && value > 1 && (value < 64 || value > 512 || value % 64 != 0))
+    return fail(RVN_EINVAL, "[raven_hip] rvn_engine_set_option: ed_wide_lanes is 64 .. 512 in steps of 64, or 1 (no workgroup ring); 0 or -1: the default");
   std::lock_guard<std::recursive_mutex> lk(h->e.mu);
   if (previous) *previous = *slot < 0 ? (is_rows ? static_cast<int>(kPoaRowsMinWindowsDefault) : -1) : *slot;  // (the value the default stands for where it has one)
   *slot = value == -1 ? ((is_rows || slot == &h->e.opt.polish_sketch_cache_mb) ? -1 : 0) : value;

@@ -77,6 +77,21 @@ __host__ __device__ inline bool overlap_finalize(Overlap& o, const PileRegion& L
   return true;
 }
 
+// the reference's keep rule on a distance x: !(1. - x / max(length) < identity), in double (construct.cc:190-199, and the
+// same rule with min_ratio in RemoveBubbles, assemble.cc:271-281)
+__host__ __device__ inline bool identity_keeps(u32 x, u32 maxlen, double identity) {
+  return !(1. - static_cast<double>(x) / static_cast<double>(maxlen) < identity);
+}
+// the largest distance that still passes it (0 where none does: the rule is then decided by the sweep's "above")
+__host__ __device__ inline u32 identity_kmax(u32 maxlen, double identity) {
+  double guess = (1. - identity) * static_cast<double>(maxlen);
+  guess = guess < 0 ? 0 : (guess > static_cast<double>(maxlen) ? static_cast<double>(maxlen) : guess);
+  u32 t = static_cast<u32>(guess);
+  while (t < maxlen && identity_keeps(t + 1, maxlen, identity)) ++t;  // the rule is monotone in the distance
+  while (t > 0 && !identity_keeps(t, maxlen, identity)) --t;
+  return t;
+}
+
 __host__ __device__ inline u32 overlap_length(const Overlap& o) {  // GetOverlapLength (overlap_utils.cc:10-12)
   const u32 a = o.rhs_end - o.rhs_begin, b = o.lhs_end - o.lhs_begin;
   return a > b ? a : b;

@@ -86,11 +86,7 @@ struct EdPairRec {
 };
 
 // edlibAlign(lhs span, rhs span [reverse-complemented on the opposite strand]) pairs of the overlaps that survived the update
-// the reference's keep rule on a distance x: !(1. - x / max(length) < identity), in double
-__device__ __forceinline__ bool identity_keeps(u32 x, u32 maxlen, double identity) {
-  return !(1. - static_cast<double>(x) / static_cast<double>(maxlen) < identity);
-}
-
+// (the reference's keep rule on a distance: identity_keeps, overlap_rules.h).
 // Also the largest distance that still passes the filter (kmax): the edit-distance stage then needs ONE sweep at that
 // threshold per pair — "exact distance if <= kmax, else above" decides the overlap exactly as the unbounded distance would.
 __global__ void ed_pairs_kernel(const Overlap* __restrict__ ovl, const u8* __restrict__ ok, const u32* __restrict__ slot,
@@ -103,12 +99,7 @@ __global__ void ed_pairs_kernel(const Overlap* __restrict__ ovl, const u8* __res
   const u32 ai = index_of ? index_of[o.lhs_id] : o.lhs_id, bi = index_of ? index_of[o.rhs_id] : o.rhs_id;
   pairs[slot[i]] = EdPairRec{ai, o.lhs_begin, a, bi, o.rhs_begin, b, o.strand ? 1u : 0u, 0u};
   const u32 maxlen = a > b ? a : b;
-  double guess = (1. - identity) * static_cast<double>(maxlen);
-  guess = guess < 0 ? 0 : (guess > static_cast<double>(maxlen) ? static_cast<double>(maxlen) : guess);
-  u32 t = static_cast<u32>(guess);
-  while (t < maxlen && identity_keeps(t + 1, maxlen, identity)) ++t;  // the rule is monotone in the distance
-  while (t > 0 && !identity_keeps(t, maxlen, identity)) --t;
-  kmax[slot[i]] = t;
+  kmax[slot[i]] = identity_kmax(maxlen, identity);
 }
 
 // score = 1 - distance / max(length) in double; overlaps below the identity threshold lose their ok flag

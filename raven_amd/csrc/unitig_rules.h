@@ -104,6 +104,11 @@ __host__ __device__ inline u64 tiling_word(const Segment* seg, const u32* cum, u
   return w;
 }
 
+// ---- the sequence of a node path (RemoveBubbles' path_sequence, RavenLib/src/assemble.cc:225-237) ----
+// what a member of `own` bases contributes: Edge::Label() = InflateData(0, label), which clamps a length beyond the
+// sequence (a wrapped edge length gives the whole node); the last member is taken whole, whatever its label
+__host__ __device__ inline u32 path_member_keep(u32 label, u32 own, bool last) { return last || label > own ? own : label; }
+
 // ---- what CreateUnitigs decides per chain (RavenLib/src/common.cc:96-112, graph.cc:53) ----
 // a chain of `nodes` nodes is made a unitig when it is circular or has 2 epsilon + 2 nodes (uint32 arithmetic, as there)
 __host__ __device__ inline bool chain_is_kept(u32 nodes, bool circular, u32 epsilon) {

@@ -297,6 +297,18 @@ __global__ void append_nodes_kernel(u32 n_new, u32 first_node, const u64* __rest
   if (jj < n_new) len[static_cast<u64>(first_node) + jj] = ulen[jj];
 }
 
+// per member of a node path: the bases it contributes (path_member_keep) and the number of its segments they keep
+__global__ void path_members_kernel(u64 n_members, const u32* __restrict__ node, const u32* __restrict__ label, const u32* __restrict__ path,
+                                    const u64* __restrict__ moff, TilingView t, u32* __restrict__ mlen, u32* __restrict__ mseg) {
+  const u64 at = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (at >= n_members) return;
+  const u32 u = node[at];
+  const u32 keep = path_member_keep(label[at], t.len[u], at + 1 == moff[path[at] + 1]);
+  const u64 s0 = t.seg_off[u];
+  mlen[at] = keep;
+  mseg[at] = prefix_segments(t.cum + s0, static_cast<u32>(t.seg_off[u + 1] - s0), keep);
+}
+
 // one lane per packed word of the output read set: read i = node nodes[i]
 __global__ void pack_tilings_kernel(const u32* __restrict__ nodes, const u64* __restrict__ woff, u32 n_reads, u64 n_words, TilingView t,
                                     const u64* __restrict__ packed, const u64* __restrict__ read_word_off, u64* __restrict__ out) {
@@ -597,6 +609,74 @@ void tiling_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, const u32
   }
   RVN_HIP(hipMemsetAsync(d_packed + n_words, 0, 16, s));
   RVN_HIP(rvn_stream_sync(s));
+  reads_finish_device_set(e, out, woff, lens, nullptr, total);
+}
+
+// A path is a node that is never appended: its segment list is built as CreateUnitigs builds a unitig's (the members'
+// prefixes one behind the other: append_segments_kernel), in a tiling of its own with one node per path, and packed by
+// pack_tilings_kernel.  What is refused is found on the host, from the node lengths it keeps, before the first launch.
+void tiling_paths_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, u32 n_paths, const u64* h_off, const u32* h_node,
+                           const u32* h_label, ReadsDev& out) {
+  const std::string who = "[raven_hip] rvn_tiling_paths_as_reads: ";
+  hipStream_t s = e.stream;
+  UnitigScratch& S = e.unitig;
+  if (T.reads_serial != R.serial) throw std::invalid_argument(who + "the tiling was made for another read set");
+  std::vector<u64> woff(static_cast<size_t>(n_paths) + 1, 0), moff(static_cast<size_t>(n_paths) + 1, 0);
+  std::vector<u32> lens(n_paths);
+  for (u32 p = 0; p < n_paths; ++p) {
+    if (h_off[p + 1] < h_off[p]) throw std::invalid_argument(who + "offsets must not decrease (path " + std::to_string(p) + ")");
+    if (h_off[p + 1] == h_off[p]) throw std::invalid_argument(who + "path " + std::to_string(p) + " is empty");
+  }
+  const u64 m0 = n_paths ? h_off[0] : 0;
+  const u64 M = n_paths ? h_off[n_paths] - m0 : 0;
+  std::vector<u32> path_of(M);
+  u64 total = 0;
+  for (u32 p = 0; p < n_paths; ++p) {
+    u64 bases = 0;
+    for (u64 i = h_off[p]; i < h_off[p + 1]; ++i) {
+      if (h_node[i] >= T.n_nodes)
+        throw std::invalid_argument(who + "node " + std::to_string(h_node[i]) + " (member " + std::to_string(i) + ") is not in the tiling");
+      bases += path_member_keep(h_label[i], T.h_len[h_node[i]], i + 1 == h_off[p + 1]);
+      path_of[i - m0] = p;
+    }
+    if (bases > 0xFFFFFFFFULL) throw std::invalid_argument(who + "path " + std::to_string(p) + " has 2^32 bases or more");
+    lens[p] = static_cast<u32>(bases);
+    total += bases;
+    woff[p + 1] = woff[p] + (bases + 31) / 32;
+    moff[p + 1] = h_off[p + 1] - m0;
+  }
+  const u64 n_words = woff[n_paths];
+  u64* d_packed = out.packed.get<u64>(n_words + 2);
+  if (n_words) {
+    // members: what each keeps, the scans of bases and segments
+    const MemberTable mt{upload(S.members, h_node + m0, M, s), upload(S.mnode, path_of.data(), M, s), S.mlen.get<u32>(M + 1),
+                         S.mseg.get<u32>(M + 1), nullptr};
+    const u32* d_label = upload(S.mcnt, h_label + m0, M, s);
+    const u64* d_moff = upload(S.moff, moff.data(), moff.size(), s);
+    const TilingView tv = view_of(T);
+    RVN_KLAUNCH(kKPathTiling, path_members_kernel<<<div_up(M, 256), 256, 0, s>>>(M, mt.node, d_label, mt.unitig, d_moff, tv, mt.len, mt.seg));
+    u64* d_lenscan = S.lenscan.get<u64>(M + 1);
+    u64* d_segscan = S.segscan.get<u64>(M + 1);
+    exclusive_scan_u32_u64(mt.len, d_lenscan, M, e.scratch.scan_tmp, s);
+    exclusive_scan_u32_u64(mt.seg, d_segscan, M, e.scratch.scan_tmp, s);
+    const u64 segs = read_back(e, d_segscan + M, 8);
+    // the paths' own tiling: node p = path p
+    Segment* d_seg = S.pseg.get<Segment>(segs + 1);
+    u32* d_cum = S.pcum.get<u32>(segs + 1);
+    u64* d_seg_off = S.pseg_off.get<u64>(static_cast<size_t>(n_paths) + 2);
+    u32* d_len = S.plen.get<u32>(static_cast<size_t>(n_paths) + 1);
+    const u32* d_lens = upload(S.ulen, lens.data(), n_paths, s);
+    RVN_KLAUNCH(kKPathTiling, append_segments_kernel<<<div_up(M, 256), 256, 0, s>>>(M, mt, d_moff, d_lenscan, d_segscan, tv, 0, d_seg, d_cum));
+    RVN_KLAUNCH(kKPathTiling, append_nodes_kernel<<<div_up(static_cast<u64>(n_paths) + 1, 256), 256, 0, s>>>(n_paths, 0, d_moff, d_segscan, 0, d_lens, d_seg_off, d_len));
+    std::vector<u32> iota(n_paths);
+    for (u32 p = 0; p < n_paths; ++p) iota[p] = p;
+    const u32* d_nodes = upload(S.nodes, iota.data(), n_paths, s);
+    const u64* d_woff = upload(S.woff, woff.data(), woff.size(), s);
+    RVN_KLAUNCH(kKPathTiling, pack_tilings_kernel<<<div_up(n_words, 256), 256, 0, s>>>(d_nodes, d_woff, n_paths, n_words, TilingView{d_seg_off, d_seg, d_cum, d_len},
+                                                             R.packed.as<u64>(), R.word_off.as<u64>(), d_packed));
+  }
+  RVN_HIP(hipMemsetAsync(d_packed + n_words, 0, 16, s));
+  RVN_HIP(rvn_stream_sync(s));  // (the host tables above are locals)
   reads_finish_device_set(e, out, woff, lens, nullptr, total);
 }
 

@@ -165,6 +165,8 @@ _SIGNATURES = {
     "rvn_unitigs_destroy": (None, [_vp]),
     "rvn_unitigs_as_reads": (_i32, [_vp, _vp, _vp, _vp, _i32, _pp]),
     "rvn_tiling_as_reads": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp]),
+    "rvn_tiling_paths_as_reads": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _pp]),
+    "rvn_path_similarity_batch": (_i32, [_vp, _vp, _vp, _u32, _dbl, _vp, _vp]),
     "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
     "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
     "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
@@ -1074,6 +1076,18 @@ class Engine:
                                              C.byref(cells)))
         return out, ms.value, cells.value
 
+    # -- RemoveBubbles' similarity test on pairs of path sequences -----------------------------------
+    def path_similarity(self, paths: Reads, pairs, min_ratio=0.8):
+        """rvn_path_similarity_batch.  pairs: n x 2 read indices of `paths` (Tiling.paths_as_reads).  Returns (uint8 similar,
+        uint32 distance: exact where it passes the rule, PATH_DISTANCE_ABOVE above it, PATH_REJECTED_BY_LENGTH where the
+        length rule rejected the pair)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        similar = np.zeros(pairs.shape[0], np.uint8)
+        distance = np.zeros(pairs.shape[0], np.uint32)
+        _check(lib().rvn_path_similarity_batch(self._h, paths._h, _p(pairs), pairs.shape[0], float(min_ratio), _p(similar),
+                                               _p(distance)))
+        return similar, distance
+
     # -- edlibAlign(NW, TASK_PATH), batched ---------------------------------------------------------
     def align_paths(self, queries: Reads, targets: Reads, pairs: np.ndarray, ops=False):
         """rvn_align_path_batch.  pairs: array of ALIGN_PAIR_DTYPE.  Returns (uint32 distances — 0xFFFFFFFF: not aligned —,
@@ -1292,6 +1306,18 @@ class Tiling:
         _check(lib().rvn_tiling_as_reads(self._e._h, self._h, self.reads._h, _p(ids), ids.shape[0], C.byref(h)))
         return _device_reads(self._e, h)
 
+    def paths_as_reads(self, offsets, nodes, labels) -> Reads:
+        """The sequences of node paths as a read set (rvn_tiling_paths_as_reads): path p = nodes[offsets[p] .. offsets[p + 1]),
+        every member but the last cut to its first min(label, length) bases."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        lb = np.ascontiguousarray(labels, dtype=np.uint32)
+        if off.shape[0] < 1 or nd.shape[0] != lb.shape[0] or (off.shape[0] > 1 and int(off.max()) > nd.shape[0]):
+            raise ValueError("paths_as_reads: array sizes do not fit the offsets")
+        h = C.c_void_p()
+        _check(lib().rvn_tiling_paths_as_reads(self._e._h, self._h, self.reads._h, off.shape[0] - 1, _p(off), _p(nd), _p(lb), C.byref(h)))
+        return _device_reads(self._e, h)
+
     def close(self):
         if self._h is not None:
             lib().rvn_tiling_destroy(self._h)
@@ -1314,6 +1340,7 @@ def _device_reads(engine, handle) -> Reads:
 
 
 UNITIGS_SELECTED, UNITIGS_ALL = 0, 1
+PATH_DISTANCE_ABOVE, PATH_REJECTED_BY_LENGTH = 0xFFFFFFFE, 0xFFFFFFFF  # Engine.path_similarity's distance codes
 
 
 class Unitigs:
