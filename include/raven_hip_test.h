@@ -98,6 +98,21 @@ int rvn_test_freelist(uint64_t size, uint64_t grain, const int64_t* ops, uint32_
  * Returns 0, RVN_EINVAL for a NULL argument or another W. */
 int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off, const uint32_t* pairs, uint32_t n,
                      const uint32_t* kmax, int W, uint32_t* out);
+/* edit_distance_dev (edit_distance.hip: the function behind rvn_edit_distance_batch, the identity filters of both passes
+ * and rvn_path_similarity_batch) ON THE DEVICE with pairs and thresholds taken from the host, so that a test chooses the
+ * route and the threshold a product door would derive.  h / reads: an engine and an uploaded read set of THIS library.
+ * pairs: n_pairs x {a_idx, a_begin, a_len, b_idx, b_begin, b_len, strand, 0}, the records of rvn_edit_distance_batch
+ * (strand 0 = the b span is reverse-complemented).  kmax (nullable): per-pair thresholds as the identity filter passes
+ * them; NULL = unbounded.  wide_sweep: 0 = the usual route (lane windows, wave ring, striped sweep), 1 = the workgroup
+ * ring of engine option ed_wide_lanes, then the striped sweep (ed_wide_lanes = 1: the usual route after all).  The hook
+ * uploads, makes ONE call of edit_distance_dev(e, r, pairs, n_pairs, out, kmax, wide_sweep != 0) and copies the values
+ * back AS STORED: the exact distance, or 0xFFFFFFFE where it is above the pair's kmax — except that a pair the striped
+ * sweep decided comes back exact even above its kmax (rvn_path_similarity_batch documents the exception).  It launches
+ * no kernel itself.  RVN_EINVAL with a message, before anything is launched: a NULL h / reads / pairs / out, a
+ * wide_sweep other than 0 / 1, and every span rvn_edit_distance_batch refuses (read index out of range, begin + len
+ * beyond the read; the same check, abi.h).  n_pairs == 0: RVN_OK, nothing runs. */
+int rvn_test_edit_distance_dev(rvn_engine* h, const rvn_reads* reads, const uint32_t* pairs, uint32_t n_pairs,
+                               const uint32_t* kmax, int wide_sweep, uint32_t* out);
 /* The probe branch of Map's match stage (map.hip: index_build_table, match_count_kernel, the scan, match_emit_kernel, the
  * gather of the segment offsets — the one function map_batch_impl calls) ON THE DEVICE with the query sketch taken from
  * the host instead of from reads.  h: an engine of THIS library whose index is built (rvn_shard_index_build or

@@ -88,6 +88,18 @@ inline void put(Engine& e, void* dst, const void* src, size_t bytes, hipMemcpyKi
   else RVN_HIP(hipMemcpy(dst, src, bytes, kind));
 }
 
+// The argument check of the span records of rvn_edit_distance_batch (and of whoever else takes them): nullptr, or what is
+// wrong with them.  Every index a kernel forms from a record stays inside the read set when this passes.
+inline const char* ed_pairs_error(const ReadsDev& rd, const rvn_ed_pair* pairs, u32 n_pairs) {
+  for (u32 i = 0; i < n_pairs; ++i) {
+    const rvn_ed_pair& p = pairs[i];
+    if (p.lhs_read >= rd.n || p.rhs_read >= rd.n || static_cast<u64>(p.lhs_begin) + p.lhs_len > rd.h_len[p.lhs_read] ||
+        static_cast<u64>(p.rhs_begin) + p.rhs_len > rd.h_len[p.rhs_read])
+      return "span outside its read";
+  }
+  return nullptr;
+}
+
 // The argument check of a CSR offsets array off[n + 1] whose lists must stay below max_len entries: nullptr, or what is
 // wrong with it (the entry point puts its name in front).
 constexpr u64 kMaxPileCells = 1ULL << 27;  // a pile's coverage / k-mer cells

@@ -421,13 +421,8 @@ int rvn_edit_distance_batch(rvn_engine* h, const rvn_reads* r, const rvn_ed_pair
   return guarded(h ? &h->e : nullptr, [&]() -> int {
     if (!h || !r || (n_pairs && (!pairs || !distances))) return fail(RVN_EINVAL, "[raven_hip] NULL argument");
     const ReadsDev& rd = r->r;
-    for (uint32_t i = 0; i < n_pairs; ++i) {
-      const rvn_ed_pair& p = pairs[i];
-      if (p.lhs_read >= rd.n || p.rhs_read >= rd.n ||
-          static_cast<u64>(p.lhs_begin) + p.lhs_len > rd.h_len[p.lhs_read] ||
-          static_cast<u64>(p.rhs_begin) + p.rhs_len > rd.h_len[p.rhs_read])
-        return fail(RVN_EINVAL, "[raven_hip] rvn_edit_distance_batch: span outside its read");
-    }
+    if (const char* what = ed_pairs_error(rd, pairs, n_pairs))
+      return fail(RVN_EINVAL, std::string("[raven_hip] rvn_edit_distance_batch: ") + what);
     RVN_HIP(hipSetDevice(h->e.device));
     UseTimers ut(h->e);
     static_assert(sizeof(rvn_ed_pair) == 32, "pair layout");

@@ -555,6 +555,28 @@ int rvn_test_engine_scratch_bytes(rvn_engine* h, uint64_t* bytes) {
   return RVN_OK;
 }
 
+// rvn_test_edit_distance_dev (include/raven_hip_test.h): the records and thresholds go up, ONE call of edit_distance_dev, the
+// stored values come back.  The buffers are the ones path_similarity_batch hands to the same function.  No kernel is
+// launched from here; every record is checked (abi.h: ed_pairs_error, as rvn_edit_distance_batch) before anything runs.
+int rvn_test_edit_distance_dev(rvn_engine* h, const rvn_reads* reads, const uint32_t* pairs, uint32_t n_pairs, const uint32_t* kmax,
+                               int wide_sweep, uint32_t* out) {
+  return guarded(h, h && reads && pairs && out, "[raven_hip] rvn_test_edit_distance_dev: NULL argument", [&](Engine& e) -> int {
+    static_assert(sizeof(rvn_ed_pair) == 32, "pair layout");
+    if (wide_sweep != 0 && wide_sweep != 1) return fail(RVN_EINVAL, "[raven_hip] rvn_test_edit_distance_dev: wide_sweep is 0 or 1");
+    if (const char* what = ed_pairs_error(reads->r, reinterpret_cast<const rvn_ed_pair*>(pairs), n_pairs))
+      return fail(RVN_EINVAL, std::string("[raven_hip] rvn_test_edit_distance_dev: ") + what);
+    if (n_pairs == 0) return RVN_OK;
+    hipStream_t s = e.stream;
+    const u32* d_pairs = upload(e.scratch.tmp_a, pairs, 8 * static_cast<size_t>(n_pairs), s);
+    const u32* d_kmax = kmax ? upload(e.scratch.tmp_c, kmax, n_pairs, s) : nullptr;
+    u32* d_out = e.scratch.tmp_b.get<u32>(static_cast<size_t>(n_pairs) + 1);
+    edit_distance_dev(e, reads->r, d_pairs, n_pairs, d_out, d_kmax, wide_sweep == 1);
+    RVN_HIP(hipMemcpyAsync(out, d_out, static_cast<size_t>(n_pairs) * 4, hipMemcpyDeviceToHost, s));
+    RVN_HIP(rvn_stream_sync(s));
+    return RVN_OK;
+  });
+}
+
 int rvn_test_low_complexity(const uint8_t* codes, uint32_t k) { return lc_kmer_passes(codes, k) ? 1 : 0; }
 
 void rvn_test_std_sort_lendesc(uint64_t* data, uint64_t n) { std_sort(data, data + n, LenDesc()); }

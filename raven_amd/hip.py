@@ -210,6 +210,7 @@ _TEST_SIGNATURES = {
     "rvn_test_inflate_fast": (_i32, [_vp, _u64, _vp, _u64, _u64, _vp]),
     "rvn_test_freelist": (_i32, [_u64, _u64, _vp, _u32, _vp, _vp]),
     "rvn_test_ed_lane": (_i32, [_vp, _vp, _vp, _u32, _vp, _i32, _vp]),
+    "rvn_test_edit_distance_dev": (_i32, [_vp, _vp, _vp, _u32, _vp, _i32, _vp]),
     "rvn_test_match_probe": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _i32, _i32, _pp, _pp, _vp, _vp, _pu64]),
     "rvn_test_radix_sort_pairs": (_i32, [_i32, _vp, _vp, _u64, _i32, _i32]),
     "rvn_test_exclusive_scan": (_i32, [_i32, _vp, _u64, _u32, _u32, _vp]),
@@ -1691,6 +1692,19 @@ class HookEngine:
             T.rvn_paths_destroy(h)
         names = ("n_aligned", "n_retries", "n_unaligned", "n_batches", "band_cells", "store_bytes")
         return dist, off, out, int(n_bad.value), plans[:pairs.shape[0]], dict(zip(names, (int(x) for x in stats)))
+
+    def edit_distance_dev(self, reads_handle, pairs, kmax=None, wide_sweep=False):
+        """rvn_test_edit_distance_dev: one call of edit_distance_dev (edit_distance.hip) on a read handle of this engine.
+        pairs: ED_PAIR_DTYPE; kmax: uint32 per pair or None (unbounded); wide_sweep: the workgroup ring's route (an int
+        other than 0 / 1 is passed on as it is, for the refusal).  Returns the uint32 values as stored: the exact distance
+        or ED_ABOVE."""
+        pairs = np.ascontiguousarray(pairs, dtype=ED_PAIR_DTYPE)
+        km = None if kmax is None else np.ascontiguousarray(kmax, dtype=np.uint32)
+        assert km is None or km.shape == pairs.shape
+        out = np.zeros(max(pairs.shape[0], 1), dtype=np.uint32)
+        _test_check(test_lib().rvn_test_edit_distance_dev(self._h, reads_handle, _p(pairs), pairs.shape[0], _p(km),
+                                                          int(wide_sweep), _p(out)))
+        return out[:pairs.shape[0]]
 
     def second_pass(self, reads_handle, n, pile_begin, pile_end, pile_invalid, identity, kmer_len, batches):
         """rvn_test_second_pass: the second pass with Map's output of every batch given by the host.  batches = list of

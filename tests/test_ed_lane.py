@@ -3,7 +3,8 @@ its bounded mode against the textbook DP of the oracle, without a GPU: the per-p
 __host__ __device__ function with no cross-lane operation, and rvn_test_ed_lane calls that very function on the host.
 
 For every pair, every window and every threshold the RAW value the kernel stores is predicted from the DP distance D and
-a threshold k_W restated here by brute force from the rule in the kernel's comment (never from ed_lane_threshold):
+a threshold k_W restated by brute force from the rule in the kernel's comment (tests/ed_lane_model.py; never from
+ed_lane_threshold):
 the exact D when D <= min(k_W, kmax), "above" when kmax decides, the window's overflow code otherwise — never a number
 that is not D, and never an overflow where the window has to decide.  TextGroups (unaligned fetch, clipping at the
 span's end, the reverse strand), PeqRaw (1 / 2 / 3-word loads, converted a cycle later), the moving window, the fits edge
@@ -21,6 +22,7 @@ import pytest
 
 from oracle import oracle
 from raven_amd import hip, seqio, synth
+from tests.ed_lane_model import expected, k_window  # (shared with tests/ed_ring_cases.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WS = (3, 5, 7)
@@ -29,35 +31,6 @@ OVER = {3: hip.ED_OVERFLOW, 5: hip.ED_OVERFLOW, 7: hip.ED_OVERFLOW_WIDE}
 INF = 1 << 40
 THREADS = min(16, os.cpu_count() or 1)
 DEC = np.frombuffer(b"ACGT", dtype=np.uint8)
-
-
-def k_window(n, m, W, _cache={}):
-    """Threshold of a window of W slots, from the kernel's rule: the largest s >= 0 with ceil(lo / 64) + ceil(hi / 64) <=
-    W - 1 for lo = s + max(m - n, 0), hi = s + max(n - m, 0); k_W = |n - m| + 2 s + 1.  None: the pair does not fit."""
-    key = (n - m, W)
-    if key not in _cache:
-        up, down, best = max(m - n, 0), max(n - m, 0), None
-        for s in range(0, 64 * W + 1):
-            if -(-(s + up) // 64) + -(-(s + down) // 64) <= W - 1:
-                best = s
-        _cache[key] = None if best is None else abs(n - m) + 2 * best + 1
-    return _cache[key]
-
-
-def expected(n, m, D, km, W):
-    """(outcome, raw value) the kernel must store; km = the pair's kmax or INF."""
-    d = abs(n - m)
-    if n == 0 or m == 0:
-        return ("empty", n + m) if n + m <= km else ("empty", ABOVE)
-    if d > km:
-        return "d_above", ABOVE
-    kw = k_window(n, m, W)
-    if kw is None:
-        return "no_fit", OVER[W]
-    k = min(kw, km)
-    if D <= k:
-        return "exact", D
-    return ("above", ABOVE) if k >= km else ("overflow", OVER[W])
 
 
 def identity_kmax(n, m, identity):

@@ -8,7 +8,9 @@ same number).  Which stage of edit_distance_dev a test reaches (asserted by laun
   batch_the_sample_turns_down   the sample's verdict "no": the main part skips the lane kernel;
   n_main_zero_one_two           2048 / 2049 / 2050 pairs;
   bounded_mode_on_the_hifi_shape   kmax through Engine.filter_overlaps_by_identity against oracle.identity_filter.
-The lane kernel's per-pair code is also stepped on the CPU against the same DP (tests/test_ed_lane.py)."""
+The lane kernel's per-pair code is also stepped on the CPU against the same DP (tests/test_ed_lane.py).
+The routes' own edges — thresholds and capacity of the wave ring, its wraps, the workgroup ring, the stripes of the full
+sweep, bounded thresholds, list sizes — are crafted in tests/ed_ring_cases.py and run by tests/test_gpu_ed_ring_cases.py."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
