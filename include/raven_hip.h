@@ -760,6 +760,34 @@ int rvn_tiling_paths_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_read
 int rvn_path_similarity_batch(rvn_engine* e, const rvn_reads* paths, const rvn_path_pair* pairs, uint32_t n_pairs, double min_ratio,
                               uint8_t* similar, uint32_t* distance);
 
+/* printEdgeSimilarity of the CSV emitters (RavenLib/src/graph_repr.cc:247-258 in PrintCsv, :358-369 in getCsv; DESIGN.md
+ * 3.15; facade: include/raven_hip/graph_repr.hpp) without a base on the host: slices of node sequences as a device read
+ * set, and the reference's score for every edge of an edge table.
+ *
+ * rvn_tiling_slices_as_reads: read i of the result is biosoup::NucleicAcid::InflateData(begin[i], length[i]) of node[i]:
+ * bases [begin, begin + min(length, length(node) - begin)), nothing when begin >= length(node) (a read of length 0).  A
+ * read set like any other (ids 0 .. n - 1), equal to rvn_reads_upload_codes of the same strings word for word.
+ * RVN_EINVAL, found before the first launch: a node that is not in the tiling, a read set other than the tiling's, slices
+ * of 2^32 packed words or more in total.  A refused call leaves the tiling as it was.  n == 0 gives an empty read set.
+ *
+ * rvn_graph_edge_similarity: per edge slot e with L = the edge's length as stored,
+ *   lhs_length[e] = length(tail) > L ? length(tail) - L : 0     (tail.InflateData(L); a wrapped L gives 0, it is not refused)
+ *   rhs_length[e] = min(lhs_length[e], length(head))            (head.InflateData(0, lhs.size()))
+ *   distance[e]   = the exact global unit-cost edit distance of the two slices (edlibAlign, default configuration; no
+ *                   threshold, any size; the other slice's length when one is empty)
+ *   score[e]      = 1 - distance / (double)lhs_length, formed in double on the host as graph_repr.cc:254 writes it: NaN for
+ *                   a live edge whose lhs is empty (0 / 0.)
+ * An empty slot (tail 0xFFFFFFFF) gets 0, 0, 0xFFFFFFFF and NaN.  Every output has n_edges entries and may be NULL.
+ * An edge whose two nodes are one segment each is swept as two spans of the reads themselves; the others' slices are
+ * packed into scratch of the engine, a chunk at a time (engine option edge_slices_budget_kb).  A distance beyond the wave
+ * ring (8 064) is swept by the workgroup ring (engine option ed_wide_lanes; up to 65 408), what lies beyond by the full sweep.
+ * RVN_EINVAL: a tiling whose node count is not the graph's, a read set other than the tiling's.  An empty graph writes
+ * nothing. */
+int rvn_tiling_slices_as_reads(rvn_engine* e, const rvn_tiling* t, const rvn_reads* reads, uint32_t n, const uint32_t* node,
+                               const uint32_t* begin, const uint32_t* length, rvn_reads** out);
+int rvn_graph_edge_similarity(rvn_engine* e, const rvn_graph* g, const rvn_tiling* t, const rvn_reads* reads,
+                              uint32_t* lhs_length, uint32_t* rhs_length, uint32_t* distance, double* score);
+
 /* Tuning a deployment may set; -1 restores the built-in default of any option (so does 0, except for poa_rows_min_windows).
  * No option changes an overlap list, a pile or a layer table; poa_rows_min_windows chooses which window-consensus kernel
  * makes the first attempt, and the two agree on 19 998 of 20 000 C4-like windows, not on every one: a
@@ -774,10 +802,13 @@ int rvn_path_similarity_batch(rvn_engine* e, const rvn_reads* paths, const rvn_p
  *   nw_stripe_lanes    alignment-path stage: the widest ring of one sweep, in lanes (1 .. 64; default 64, a whole wave).  A band
  *                      wider than that ring is swept in stripes of that many lanes (at most 8 rings: 262 144 rows by default);
  *                      smaller values force striping on small inputs; same records either way
- *   ed_wide_lanes      rvn_path_similarity_batch: lanes of the workgroup ring that sweeps thresholds beyond the wave ring (64 .. 512
+ *   ed_wide_lanes      rvn_path_similarity_batch, rvn_graph_edge_similarity: lanes of the workgroup ring that sweeps thresholds beyond the wave ring (64 .. 512
  *                      in steps of 64; default 512 = thresholds up to 65 408); 1 = no such sweep, those pairs take the usual
  *                      route to the full sweep; smaller rings reach their limit on small inputs; same verdicts and distances
  *                      either way.  Any other value is refused
+ *   edge_slices_budget_kb  rvn_graph_edge_similarity: HBM, in KB, for the packed slices of one chunk of the edges whose nodes have
+ *                      several segments (default: a quarter of the largest free block the arena, or the driver, reports;
+ *                      a chunk always holds one edge at least); same values either way
  *   index_direct_min_keys  index: distinct values from which all 4^k possible values are addressed directly (an 8-GB table at
  *                      k = 15, one cache line per probe; default 8 388 608; 1 = every index with k <= 15); same matches either way
  *   poa_rows_min_windows  window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (default 8 192;

@@ -1,7 +1,8 @@
 // abi_graph.hip — C ABI (include/raven_hip.h): the assembly graph on the device (graph.hip): rvn_construct_assembly_graph,
 // rvn_graph_from_edges, the marking of transitive and long edges, and what a graph handle gives back; node sequences as
 // tilings, rvn_graph_create_unitigs and unitig sequences as read sets (unitigs.hip); node paths as read sets and
-// RemoveBubbles' similarity verdict on pairs of them (unitigs.hip, edit_distance.hip).
+// RemoveBubbles' similarity verdict on pairs of them (unitigs.hip, edit_distance.hip); slices of nodes as read sets and the
+// CSV emitters' edge similarity (unitigs.hip, edge_similarity.hip).
 #include <cmath>
 #include <cstring>
 
@@ -307,6 +308,38 @@ int rvn_path_similarity_batch(rvn_engine* h, const rvn_reads* paths, const rvn_p
   return guarded(h, args_ok, "[raven_hip] rvn_path_similarity_batch: NULL argument", [&](Engine& e) -> int {
     static_assert(sizeof(rvn_path_pair) == 8, "a pair is two read indices");
     path_similarity_batch(e, paths->r, reinterpret_cast<const u32*>(pairs), n_pairs, min_ratio, similar, distance);
+    return RVN_OK;
+  });
+}
+
+int rvn_tiling_slices_as_reads(rvn_engine* h, const rvn_tiling* t, const rvn_reads* reads, uint32_t n, const uint32_t* node,
+                               const uint32_t* begin, const uint32_t* length, rvn_reads** out) {
+  const bool args_ok = h && t && reads && out && (n == 0 || (node && begin && length));
+  return guarded(h, args_ok, "[raven_hip] rvn_tiling_slices_as_reads: NULL argument", [&](Engine& e) -> int {
+    *out = nullptr;
+    if (t->device != e.device) return fail(RVN_EINVAL, "[raven_hip] rvn_tiling_slices_as_reads: the tiling lives on another device");
+    std::unique_ptr<rvn_reads> rr(new rvn_reads());
+    tiling_slices_as_reads(e, t->t, reads->r, n, node, begin, length, rr->r);
+    *out = rr.release();
+    return RVN_OK;
+  });
+}
+
+int rvn_graph_edge_similarity(rvn_engine* h, const rvn_graph* g, const rvn_tiling* t, const rvn_reads* reads, uint32_t* lhs_length,
+                              uint32_t* rhs_length, uint32_t* distance, double* score) {
+  return guarded(h, h && g && t && reads, "[raven_hip] rvn_graph_edge_similarity: NULL argument", [&](Engine& e) -> int {
+    if (g->device != e.device || t->device != e.device)
+      return fail(RVN_EINVAL, "[raven_hip] rvn_graph_edge_similarity: the graph or the tiling lives on another device");
+    const u64 E = g->g.n_edges;
+    // the score needs both numbers, whichever of them the caller wants
+    std::vector<u32> own_lhs, own_dist;
+    u32* lhs = lhs_length;
+    u32* dist = distance;
+    if (score && !lhs) own_lhs.resize(E), lhs = own_lhs.data();
+    if (score && !dist) own_dist.resize(E), dist = own_dist.data();
+    graph_edge_similarity(e, g->g, t->t, reads->r, lhs, rhs_length, dist);
+    if (score)  // graph_repr.cc:254, in double on the host (this unit is built without fast-math); an empty slot has no score
+      for (u64 i = 0; i < E; ++i) score[i] = dist[i] == 0xFFFFFFFFu ? std::nan("") : 1 - dist[i] / static_cast<double>(lhs[i]);
     return RVN_OK;
   });
 }

@@ -7,7 +7,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 # RVN_NO_EDLIB_SYMBOLS=1: leave the edlibAlign drop-in out (a process that also loads a real shared edlib: INTEGRATION.md 3.1)
 EDLIB=edlib_dropin
 if [ -n "${RVN_NO_EDLIB_SYMBOLS:-}" ]; then EDLIB=""; rm -f "$HERE/obj/edlib_dropin.o"; fi
-PRODUCT="scan radix_sort sketch index map chain pile edit_distance poa poa2 poa4 polish nwpath pass2 repeats resolve layout graph unitigs io shard group devpool engine abi_reads abi_overlap abi_polish abi_layout abi_graph abi_shard $EDLIB"
+PRODUCT="scan radix_sort sketch index map chain pile edit_distance poa poa2 poa4 polish nwpath pass2 repeats resolve layout graph unitigs edge_similarity io shard group devpool engine abi_reads abi_overlap abi_polish abi_layout abi_graph abi_shard $EDLIB"
 # libraven_hip_test.so (TEST INFRASTRUCTURE, include/raven_hip_test.h): every source compiled again under
 # -DRVN_TEST_HOOKS (rvn_test_*, rvn_poa_banded_emulate) -DRVN_DEBUG_KNOBS (the environment switches of experiments and
 # diagnostics: common.h knob() — the product library reads none) + the units that exist only there: the host wavefront

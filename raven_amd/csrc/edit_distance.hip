@@ -694,7 +694,10 @@ extern "C" int rvn_test_ed_lane(const uint64_t* packed, const uint64_t* word_off
 // d_kmax (nullable): per-pair thresholds — distances above them come back as 0xFFFFFFFE (see ed_banded_kernel).
 // wide_sweep: the caller's thresholds lie beyond the wave ring; the pairs go to the workgroup ring (ed_wide_kernel) and from
 // there to the full sweep, not through the lane windows and the wave ring (engine option ed_wide_lanes = 1: the usual route).
-void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32 n_pairs, u32* d_out, const u32* d_kmax, bool wide_sweep) {
+// wide_after: the usual route, but what the wave ring's sweeps leave as overflow is swept once by the workgroup ring at its
+// capacity before the full sweep (one wave) gets the rest: unbounded distances beyond 8 064 (graph_edge_similarity).
+void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32 n_pairs, u32* d_out, const u32* d_kmax, bool wide_sweep,
+                       bool wide_after) {
   if (n_pairs == 0) return;
   hipStream_t s = e.stream;
   const EdPair* d_pairs = reinterpret_cast<const EdPair*>(d_pairs_raw);
@@ -786,6 +789,18 @@ void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs_raw, u32
   if (n_todo == 0) return;
   RVN_KLAUNCH(kKEditBanded, ed_banded_kernel<4><<<div_up(n_todo, 4), 256, 0, s>>>(
                                 r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, d_todo, n_todo, d_kmax, d_out));
+  if (wide_after && e.opt.ed_wide_lanes != 1) {
+    // ---- stage 2b (this caller only): the wave ring's overflow, one sweep of the workgroup ring at its capacity ----
+    RVN_HIP(hipMemsetAsync(d_cnt, 0, 4, s));
+    ed_collect_overflow_kernel<<<div_up(n_pairs, 256), 256, 0, s>>>(d_out, n_pairs, true, d_todo, d_cnt);
+    RVN_LAUNCH_CHECK();
+    const u32 n_wide = static_cast<u32>(read_back(e, d_cnt, 4));
+    if (n_wide == 0) return;
+    const long long asked = e.opt.ed_wide_lanes;
+    const u32 lanes = asked >= 64 && asked <= kEdWideMaxLanes ? static_cast<u32>(asked) : static_cast<u32>(kEdWideMaxLanes);
+    RVN_KLAUNCH(kKEditWide, ed_wide_kernel<4><<<n_wide, lanes, 0, s>>>(r.packed.as<u64>(), r.word_off.as<u64>(), d_pairs, d_todo, n_wide,
+                                                                       d_kmax, d_out));
+  }
   }
   // ---- stage 3: pairs beyond the ring capacity (rare): unbanded striped sweep, exact ----
   RVN_HIP(hipMemsetAsync(d_cnt, 0, 4, s));

@@ -129,6 +129,8 @@ struct EngineOptions {
                                      // wider than that is swept in stripes of that many super-blocks (nwpath.h).  Same records either way
   long long ed_wide_lanes = 0;       // path similarity: lanes of the workgroup ring that sweeps thresholds beyond the wave ring (64 .. 512 in
                                      // steps of 64, default 512); 1 = no such sweep, those pairs are the full sweep's.  Same distances either way
+  long long edge_slices_budget_kb = 0;  // edge similarity: HBM for the packed slices of one chunk of the edges whose nodes are tilings of several
+                                     // segments (default: a quarter of the largest free block the arena, or the driver, reports).  Same values either way
   long long index_direct_min_keys = 0;  // index: distinct values from which every possible value is addressed directly (index.hip; default 8 M,
                                      // 1 = every index with 2k <= 30 bits — the tests of that path on small inputs).  Same matches either way
   long long poa_rows_min_windows = -1;  // window-consensus stage: smallest batch that starts with the rows-on-lanes kernel (poa4.hip);
@@ -271,8 +273,10 @@ void edit_distance_batch(Engine& e, const ReadsDev& r, const u32* h_pairs, u32 n
 // the same with pairs and distances resident in HBM (pass2.hip: identity filters)
 // wide_sweep: the pairs' thresholds lie beyond the wave ring; they go straight to the ring over a workgroup's lanes and
 // from there to the full sweep (path_similarity_batch alone asks for it, for that part of its pairs)
+// wide_after: what the wave ring's doubling sweeps leave as overflow goes to the workgroup ring in one sweep at its capacity
+// before the full sweep takes the rest (graph_edge_similarity alone asks for it: unbounded distances beyond 8 064)
 void edit_distance_dev(Engine& e, const ReadsDev& r, const u32* d_pairs, u32 n_pairs, u32* d_out, const u32* d_kmax = nullptr,
-                       bool wide_sweep = false);
+                       bool wide_sweep = false, bool wide_after = false);
 
 // window consensus (poa.hip): scratch of a batch, which kernels run (tests), and what the last batch / all batches did
 struct PoaState {
@@ -704,6 +708,27 @@ void tiling_paths_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, u32
 // may be nullptr
 void path_similarity_batch(Engine& e, const ReadsDev& P, const u32* h_pairs, u32 n_pairs, double min_ratio, u8* h_similar,
                            u32* h_distance);
+// InflateData(begin[i], length[i]) of node node[i] as read i of a read set (unitig_rules.h: slice_length, slice_word)
+void tiling_slices_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, u32 n, const u32* h_node, const u32* h_begin,
+                            const u32* h_length, ReadsDev& out);
+// its packing with everything in HBM: slices [first, first + count) of the lists, d_woff[s] = first word of slice s in a
+// numbering that starts anywhere; the words of the range go to d_out[0 ..) (one lane per word, site slice_pack)
+void pack_slices_dev(Engine& e, const TilingDev& T, const ReadsDev& R, const u32* d_node, const u32* d_begin, const u32* d_length,
+                     const u64* d_woff, u64 first, u64 count, u64 n_words, u64* d_out);
+// The edge similarity of the CSV emitters (RavenLib/src/graph_repr.cc:247-254) for every slot of an edge table
+// (edge_similarity.hip): the two slices' lengths and their exact edit distance; empty slot: 0, 0, 0xFFFFFFFF.  Host arrays
+// of n_edges entries, each may be nullptr.
+struct EdgeSimScratch {
+  DevBuf lhs, rhs, dist, direct, mat, dslot, mslot, dids, mids, pairs, ddist, snode, sbegin, slen, swords, woff, bounds, wbase;
+  DevBuf cpairs, cdist;
+  ReadsDev slices;  // the scratch read set of one chunk: packed words and word offsets only
+  void for_each_buf(const BufFn& f) {
+    f(lhs), f(rhs), f(dist), f(direct), f(mat), f(dslot), f(mslot), f(dids), f(mids), f(pairs), f(ddist), f(snode), f(sbegin), f(slen);
+    f(swords), f(woff), f(bounds), f(wbase), f(cpairs), f(cdist), f(slices.packed), f(slices.word_off);
+  }
+  void release() { release_bufs(*this); }
+};
+void graph_edge_similarity(Engine& e, const GraphDev& g, const TilingDev& T, const ReadsDev& R, u32* h_lhs, u32* h_rhs, u32* h_distance);
 // what every device-made read set shares once its packed words lie in r.packed (abi_reads.hip): the tables, the ids, the tiles
 void reads_finish_device_set(Engine& e, ReadsDev& r, const std::vector<u64>& woff, const std::vector<u32>& lens, const uint32_t* ids,
                              u64 total_bases);
@@ -730,11 +755,12 @@ struct Engine {
   IoState io;
   GraphScratch graph;
   UnitigScratch unitig;
+  EdgeSimScratch edge_sim;
   SharedScratch scratch;
   // every group that owns device buffers (what engine_release_scratch releases)
   template <typename F>
   void for_each_group(F&& f) {
-    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(graph), f(unitig), f(scratch);
+    f(sketch), f(map), f(shard), f(ed), f(p2), f(poa), f(nw), f(polish), f(io), f(graph), f(unitig), f(edge_sim), f(scratch);
   }
   int stage_kind = 0;   // the stage entry point running (engine_release_scratch_if_tight)
   u32 oom_mask = 0;     // kinds of stages that ran out of device memory once: they start from released scratch

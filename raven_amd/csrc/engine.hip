@@ -99,7 +99,7 @@ void fetch_values(Engine& e, const DevBuf& val, u64 n, u64* values) {
 }
 
 const char* engine_option_names() {
-  return "nw_budget_mb, nw_group_walk, nw_stripe_lanes, ed_wide_lanes, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
+  return "nw_budget_mb, nw_group_walk, nw_stripe_lanes, ed_wide_lanes, edge_slices_budget_kb, index_direct_min_keys, poa_rows_min_windows, io_threads, io_slab_mb, io_ring, io_zlib, arena_mb, arena_margin_mb, "
          "no_arena, release_always, polish_join, polish_sketch_cache_mb";
 }
 long long* engine_option(EngineOptions& o, const char* name) {
@@ -108,6 +108,7 @@ long long* engine_option(EngineOptions& o, const char* name) {
   if (n == "nw_group_walk") return &o.nw_group_walk;
   if (n == "nw_stripe_lanes") return &o.nw_stripe_lanes;
   if (n == "ed_wide_lanes") return &o.ed_wide_lanes;
+  if (n == "edge_slices_budget_kb") return &o.edge_slices_budget_kb;
   if (n == "index_direct_min_keys") return &o.index_direct_min_keys;
   if (n == "poa_rows_min_windows") return &o.poa_rows_min_windows;
   if (n == "io_threads") return &o.io_threads;

@@ -9,6 +9,8 @@
 //   prefix_segments   the number of segments a prefix of a tiling keeps
 //   tiling_word       one packed 64-bit word (32 bases, base x at bits 2x .. 2x + 1, zero above the last base) of a
 //                     tiling's sequence from the 2-bit packed reads, reverse complement included
+//   slice_length, segment_slice, slice_word    InflateData(i, len) of a node; edge_lhs_length / edge_rhs_length: the two
+//                     slices of an edge's similarity (graph_repr.cc:248-249)
 // Codes are A C G T = 0 1 2 3, so the complement of a code is code ^ 3.
 #pragma once
 
@@ -103,6 +105,34 @@ __host__ __device__ inline u64 tiling_word(const Segment* seg, const u32* cum, u
   }
   return w;
 }
+
+// ---- slices: biosoup::NucleicAcid::InflateData(i, len) on a tiling ----
+// the bases of a node of `own` bases that InflateData(i, len) returns: [i, i + slice_length), nothing from i >= own on
+__host__ __device__ inline u32 slice_length(u32 own, u32 i, u32 len) {
+  if (i >= own) return 0;
+  return len < own - i ? len : own - i;
+}
+// bases [o, o + L) of one segment (o + L <= s.length) as a segment of its own.  On strand 1 the segment reads its stretch
+// backwards, so the slice is the reverse complement of the MIRRORED stretch: the L bases that end o bases in front of the
+// stretch's end.  segment_slice(s, 0, L) == segment_prefix(s, L).
+__host__ __device__ inline Segment segment_slice(const Segment& s, u32 o, u32 L) {
+  Segment p = s;
+  p.length = L;
+  p.begin = s.strand ? s.begin + (s.length - o - L) : s.begin + o;
+  return p;
+}
+// packed word w of the slice [i, i + L) of a tiling (L = slice_length(...), 32 w < L): the tiling's bases from i + 32 w on,
+// cut at the slice's end — tiling_word of the tiling shortened to i + L bases, which is zero above the last base
+__host__ __device__ inline u64 slice_word(const Segment* seg, const u32* cum, u32 n, u32 i, u32 L, u32 w, const u64* packed,
+                                          const u64* word_off) {
+  return tiling_word(seg, cum, n, i + L, i + 32u * w, packed, word_off);
+}
+// The two strings of an edge's similarity (RavenLib/src/graph_repr.cc:248-249): lhs = tail.InflateData(length), rhs =
+// head.InflateData(0, lhs.size()).  A length at or beyond the tail's end (a wrapped one included) gives an empty lhs.
+__host__ __device__ inline u32 edge_lhs_length(u32 tail_len, u32 edge_length) {
+  return tail_len > edge_length ? tail_len - edge_length : 0;
+}
+__host__ __device__ inline u32 edge_rhs_length(u32 lhs_len, u32 head_len) { return lhs_len < head_len ? lhs_len : head_len; }
 
 // ---- the sequence of a node path (RemoveBubbles' path_sequence, RavenLib/src/assemble.cc:225-237) ----
 // what a member of `own` bases contributes: Edge::Label() = InflateData(0, label), which clamps a length beyond the

@@ -326,6 +326,26 @@ __global__ void pack_tilings_kernel(const u32* __restrict__ nodes, const u64* __
                         packed, read_word_off);
 }
 
+// one lane per packed word of slices [first, first + count) of the lists: slice s = InflateData(begin[s], length[s]) of
+// node[s] with length[s] already clamped (slice_length); woff[s] = its first word, base = woff[first]
+__global__ void pack_slices_kernel(const u32* __restrict__ node, const u32* __restrict__ begin, const u32* __restrict__ length,
+                                   const u64* __restrict__ woff, u64 first, u64 count, u64 n_words, TilingView t,
+                                   const u64* __restrict__ packed, const u64* __restrict__ read_word_off, u64* __restrict__ out) {
+  const u64 wi = static_cast<u64>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (wi >= n_words) return;
+  const u64 at = woff[first] + wi;
+  u64 lo = first, hi = first + count;  // the slice of this word: the last s with woff[s] <= at (slices of no words own none)
+  while (hi - lo > 1) {
+    const u64 mid = lo + (hi - lo) / 2;
+    if (woff[mid] <= at) lo = mid;
+    else hi = mid;
+  }
+  const u32 u = node[lo];
+  const u64 s0 = t.seg_off[u];
+  out[wi] = slice_word(t.seg + s0, t.cum + s0, static_cast<u32>(t.seg_off[u + 1] - s0), begin[lo], length[lo], static_cast<u32>(at - woff[lo]),
+                       packed, read_word_off);
+}
+
 int rounds_for(u32 n) {  // ceil(log2 n) + 1
   int r = 0;
   while (r < 32 && (1ULL << r) < n) ++r;
@@ -609,6 +629,44 @@ void tiling_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, const u32
   }
   RVN_HIP(hipMemsetAsync(d_packed + n_words, 0, 16, s));
   RVN_HIP(rvn_stream_sync(s));
+  reads_finish_device_set(e, out, woff, lens, nullptr, total);
+}
+
+void pack_slices_dev(Engine& e, const TilingDev& T, const ReadsDev& R, const u32* d_node, const u32* d_begin, const u32* d_length,
+                     const u64* d_woff, u64 first, u64 count, u64 n_words, u64* d_out) {
+  if (n_words == 0) return;
+  RVN_KLAUNCH(kKSlicePack, pack_slices_kernel<<<div_up(n_words, 256), 256, 0, e.stream>>>(d_node, d_begin, d_length, d_woff, first, count, n_words,
+                                                                                          view_of(T), R.packed.as<u64>(), R.word_off.as<u64>(), d_out));
+}
+
+// What is refused is found on the host, from the node lengths the tiling keeps, before the first launch.
+void tiling_slices_as_reads(Engine& e, const TilingDev& T, const ReadsDev& R, u32 n, const u32* h_node, const u32* h_begin,
+                            const u32* h_length, ReadsDev& out) {
+  const std::string who = "[raven_hip] rvn_tiling_slices_as_reads: ";
+  hipStream_t s = e.stream;
+  UnitigScratch& S = e.unitig;
+  if (T.reads_serial != R.serial) throw std::invalid_argument(who + "the tiling was made for another read set");
+  std::vector<u64> woff(static_cast<size_t>(n) + 1, 0);
+  std::vector<u32> lens(n);
+  u64 total = 0;
+  for (u32 i = 0; i < n; ++i) {
+    if (h_node[i] >= T.n_nodes) throw std::invalid_argument(who + "node " + std::to_string(h_node[i]) + " (slice " + std::to_string(i) + ") is not in the tiling");
+    lens[i] = slice_length(T.h_len[h_node[i]], h_begin[i], h_length[i]);
+    total += lens[i];
+    woff[i + 1] = woff[i] + (static_cast<u64>(lens[i]) + 31) / 32;
+  }
+  const u64 n_words = woff[n];
+  if (n_words >= (1ULL << 32)) throw std::invalid_argument(who + "the slices have 2^32 packed words or more");
+  u64* d_packed = out.packed.get<u64>(n_words + 2);
+  if (n_words) {
+    const u32* d_node = upload(S.nodes, h_node, n, s);
+    const u32* d_begin = upload(S.mlen, h_begin, n, s);
+    const u32* d_len = upload(S.mseg, lens.data(), n, s);
+    const u64* d_woff = upload(S.woff, woff.data(), woff.size(), s);
+    pack_slices_dev(e, T, R, d_node, d_begin, d_len, d_woff, 0, n, n_words, d_packed);
+  }
+  RVN_HIP(hipMemsetAsync(d_packed + n_words, 0, 16, s));
+  RVN_HIP(rvn_stream_sync(s));  // (the host tables above are locals)
   reads_finish_device_set(e, out, woff, lens, nullptr, total);
 }
 

@@ -167,6 +167,8 @@ _SIGNATURES = {
     "rvn_tiling_as_reads": (_i32, [_vp, _vp, _vp, _vp, _u32, _pp]),
     "rvn_tiling_paths_as_reads": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _pp]),
     "rvn_path_similarity_batch": (_i32, [_vp, _vp, _vp, _u32, _dbl, _vp, _vp]),
+    "rvn_tiling_slices_as_reads": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _pp]),
+    "rvn_graph_edge_similarity": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rvn_engine_set_option": (_i32, [_vp, _cstr, _i64, _vp]),
     "rvn_polish_set_chunk_windows": (_u64, [_vp, _u64]),
     "rvn_polish_fetch_layers": (_i32, [_vp, _vp, _u64, _pu64]),
@@ -1254,6 +1256,17 @@ class Graph:
         _check(lib().rvn_graph_mark_long_edges(self._e._h, self._h, _p(w), _p(flags), C.byref(n)))
         return flags, n.value
 
+    def edge_similarity(self, tiling):
+        """printEdgeSimilarity of the CSV emitters for every edge slot (rvn_graph_edge_similarity): dict(lhs_length,
+        rhs_length, distance uint32 — EDGE_SLOT_EMPTY for an empty slot —, score float64 = 1 - distance / lhs_length, NaN
+        where lhs_length is 0 or the slot is empty)."""
+        E = self.n_edges
+        r = dict(lhs_length=np.zeros(E, np.uint32), rhs_length=np.zeros(E, np.uint32), distance=np.zeros(E, np.uint32),
+                 score=np.zeros(E, np.float64))
+        _check(lib().rvn_graph_edge_similarity(self._e._h, self._h, tiling._h, tiling.reads._h, _p(r["lhs_length"]),
+                                               _p(r["rhs_length"]), _p(r["distance"]), _p(r["score"])))
+        return r
+
     def create_unitigs(self, tiling, count, coverage, epsilon=0, min_unitig_size=9999):
         """raven::CreateUnitigs on the edge table (rvn_graph_create_unitigs): count / coverage per node.  The tiling grows
         by the new nodes; returns a Unitigs."""
@@ -1307,6 +1320,17 @@ class Tiling:
         _check(lib().rvn_tiling_as_reads(self._e._h, self._h, self.reads._h, _p(ids), ids.shape[0], C.byref(h)))
         return _device_reads(self._e, h)
 
+    def slices_as_reads(self, nodes, begins, lengths) -> Reads:
+        """InflateData(begins[i], lengths[i]) of nodes[i] as read i of a read set (rvn_tiling_slices_as_reads)."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        bg = np.ascontiguousarray(begins, dtype=np.uint32)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if not (nd.shape[0] == bg.shape[0] == ln.shape[0]):
+            raise ValueError("slices_as_reads: the three arrays differ in size")
+        h = C.c_void_p()
+        _check(lib().rvn_tiling_slices_as_reads(self._e._h, self._h, self.reads._h, nd.shape[0], _p(nd), _p(bg), _p(ln), C.byref(h)))
+        return _device_reads(self._e, h)
+
     def paths_as_reads(self, offsets, nodes, labels) -> Reads:
         """The sequences of node paths as a read set (rvn_tiling_paths_as_reads): path p = nodes[offsets[p] .. offsets[p + 1]),
         every member but the last cut to its first min(label, length) bases."""
@@ -1342,6 +1366,7 @@ def _device_reads(engine, handle) -> Reads:
 
 UNITIGS_SELECTED, UNITIGS_ALL = 0, 1
 PATH_DISTANCE_ABOVE, PATH_REJECTED_BY_LENGTH = 0xFFFFFFFE, 0xFFFFFFFF  # Engine.path_similarity's distance codes
+EDGE_SLOT_EMPTY = 0xFFFFFFFF  # Graph.edge_similarity's distance of an empty edge slot
 
 
 class Unitigs:
