@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds libraven_hip.so for gfx950 in-tree (raven_amd/lib/). hipcc cross-compiles without a GPU.
 # This file is the ONE list of the translation units: `build.sh --print-units` prints it ("product: ..." and
-# "test_only: ..." — NAME stands for NAME.hip) for whoever else has to compile them (the sanitizer test, tools/poa4_exp.sh).
+# "test_only: ..." — NAME stands for NAME.hip) for whoever else has to compile them (the sanitizer test).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 # RVN_NO_EDLIB_SYMBOLS=1: leave the edlibAlign drop-in out (a process that also loads a real shared edlib: INTEGRATION.md 3.1)

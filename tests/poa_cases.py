@@ -20,7 +20,8 @@ cases() returns a list of dicts:
 Sizes at a boundary are found from the oracle's statistics (a generator grows its window until the statistic is the
 one wanted); nothing here runs a kernel, and nothing looks at what a kernel returns.
 
-The limits, restated (a change of one of them in the kernels must be followed here, by hand):"""
+The limits, restated (a change of one of them in the kernels must be followed here: tests/test_poa4_limits.py
+holds the poa4 ones to raven_amd/csrc/poa4_limits.h):"""
 import functools
 import operator
 
@@ -28,33 +29,34 @@ import numpy as np
 
 from oracle import oracle
 
-P4_RING = 22         # poa4.hip:55   P4::kRing: an in-edge of at most kRing - 1 ranks (poa4.hip:2053)
-P4_RING_OVF = 20     # poa4.hip:2076 / 2079: in-edges 7..14 of a row of >= 9 (and its in-edge 7, lbk7) at most kRing - 2 ranks
-P4_MAX_D = 8         # poa4.hip:59   P4::kMaxD: band-start difference along an in-edge (poa4.hip:2053)
-P4_EDGES = 8         # poa4.hip:60   P4::kEdges: in-edges in a row descriptor (the eighth is the `v7` bit)
-P4_EDGES_MAX = 15    # poa4.hip:62   P4::kEdgesMax: a row of 16 hands the window on with reason 3 (poa4.hip:2090)
+# (poa4_limits.h: struct P4; `edge`: the lambda of poa4_phase_desc_onewave, poa4_desc.h, that looks at one in-edge)
+P4_RING = 22         # poa4_limits.h P4::kRing: an in-edge of at most kRing - 1 ranks (`edge`)
+P4_RING_OVF = 20     # `edge`: in-edges 7..14 of a row of >= 9 (and its in-edge 7, lbk7) at most kRing - 2 ranks
+P4_MAX_D = 8         # poa4_limits.h P4::kMaxD: band-start difference along an in-edge (`edge`)
+P4_EDGES = 8         # poa4_limits.h P4::kEdges: in-edges in a row descriptor (the eighth is the `v7` bit)
+P4_EDGES_MAX = 15    # poa4_limits.h P4::kEdgesMax: a row of 16 hands the window on with reason 3 (poa4_phase_desc_onewave)
 P2_RING = 32         # poa2_window.h:14 kRing: a predecessor more than 32 computed rows back is status 7 (poa2_window.h:337)
 MAX_IN = 16          # poa.h:15      kPoaMaxIn: a seventeenth in-edge is status 3
 NMAX_FLOOR, NMAX_PER_BASE = 512, 6  # poa.hip:656 nmax = clamp(6 x backbone, 512, 8192): one node more is status 2
 P2_MAX_SEQ = 896     # poa.h:18      kPoa2MaxSeq: a longer layer is the full-matrix kernel's
 MAX_SEQ = 1024       # poa.h:16      kPoaMaxSeq: a longer layer is status 4
-BANDS = (32, 64, 128, 256)  # poa4.hip:54 kBand, poa2.hip's 64 x NCH columns
-R_EDGE, R_INDEG, R_WALK = 7, 3, 10  # reasons (status bits 24-27) of poa4.hip:2173 and :2218
+BANDS = (32, 64, 128, 256)  # poa4_limits.h P4::kBand, poa2.hip's 64 x NCH columns
+R_EDGE, R_INDEG, R_WALK = 7, 3, 10  # reasons (status bits 24-27) of poa4.hip poa4_phase_dp and poa4_phase_tb
 
 # Limits of the issue's table that have NO case, because another check always fires first (DESIGN.md 3.6 repeats this):
-#  * `lbk > rho` (poa4.hip:2053, the tail of an in-edge below the layer's rank range): an in-edge is looked at only if its
-#    tail is marked (poa4.hip:2085/2088 `inside`), and r_lo is the smallest rank of a marked node (poa4.hip:1836), so
+#  * `lbk > rho` (`edge`, the tail of an in-edge below the layer's rank range): an in-edge is looked at only if its
+#    tail is marked (its `inside`), and r_lo is the smallest rank of a marked node (poa4_desc.h poa4_subgraph_marks), so
 #    rank(tail) >= r_lo and lbk = r - rank(tail) <= r - r_lo = rho for every edge that reaches the comparison.  The
 #    `below_range` family pins what CAN happen: in-edges cut by the subgraph with the tail one rank inside / below.
-#  * the step budget, reason 1 (poa4.hip:2166): t_end = max(Srow) + 17 with Srow = rho + rho / 16 + sdiff / 2 + 1
-#    (poa4.hip:2114), rho < nmax and sdiff <= lmax, so t_end + 8 <= nmax + nmax / 16 + lmax / 2 + 26 < poa4_steps().
-#  * reason 9 (poa4.hip:2185, the last column in no end node's band): backbone node `end` is an end node of every
+#  * the step budget, reason 1 (poa4.hip poa4_phase_dp): t_end = max(Srow) + 17 with Srow = rho + rho / 16 + sdiff / 2 + 1
+#    (poa4_phase_desc_onewave), rho < nmax and sdiff <= lmax, so t_end + 8 <= nmax + nmax / 16 + lmax / 2 + 26 < poa4_steps().
+#  * reason 9 (poa4.hip poa4_phase_dp, the last column in no end node's band): backbone node `end` is an end node of every
 #    (sub)graph, its guide position is `span`, where the guide is the layer's length, and poa4_band_start clamps the band
 #    to hold the last column — the straight guide rvn_poa_consensus_batch fills in cannot miss it.
-#  * reason 11 (poa4.hip:2218, a backpointer the walk cannot follow) is a consistency check, not a limit: no legal input
-#    is known to reach it.
-#  * status 3 out of poa4.hip itself (poa4.hip:1350): the layer that would add a seventeenth in-edge is aligned to a row
-#    of sixteen first, which is reason 3; the 64-column kernel reports the status 3.
+#  * reason 11 (poa4.hip poa4_phase_tb, a backpointer the walk cannot follow) is a consistency check, not a limit: no
+#    legal input is known to reach it.
+#  * status 3 out of the first attempt itself (poa4_graph.h poa4_update_graph): the layer that would add a seventeenth
+#    in-edge is aligned to a row of sixteen first, which is reason 3; the 64-column kernel reports the status 3.
 #  * P4::kMaxD 8 against 9: band starts are even (poa4_band_start), so a difference is 8 or 10: `band_step` pins those.
 FAMILIES = ("in_edge_ranks", "band_step", "in_degree", "below_range", "nodes", "length", "band", "ties", "groups")
 

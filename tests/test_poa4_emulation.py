@@ -198,7 +198,7 @@ def test_limits_are_reported():
 
 @pytest.mark.parametrize("fill", [1, 3, 2], ids=["off_diagonal_scores", "band_edge_scores", "huge_scores"])
 def test_what_the_score_ring_holds_beside_a_band_does_not_matter(fill, monkeypatch):
-    """A ring row is the 32 cells of its band, addressed by the column (poa4.hip): a read right of a
+    """A ring row is the 32 cells of its band, addressed by the column (poa4_layout.h): a read right of a
     predecessor's band, or left of it in a first column, finds another cell of that ring row where rounds 3-4 kept pads of
     -inf.  The claim is that this can only send a window on to the 64-column kernel, never change a consensus: a raised
     candidate that wins is followed by the traceback out of the band and found out.  Here the rings start every layer as
@@ -251,7 +251,7 @@ def test_rows_of_nine_to_fifteen_in_edges(fill, monkeypatch):
     """A graph row with more than eight in-edges used to send its window to the 64-column kernel (241 of the 244 windows a C4
     round handed on: a second launch behind the persistent one).  Such a row now keeps in-edges 7..14 in an overflow record;
     the NW's rare path folds them as a second group and a per-row mask tells the traceback which group a code counts in
-    (poa4.hip, P4::kEdgesMax).  The clean windows here have a row of >= 9 in-edges by construction (the kernel before this
+    (poa4_nw.h; poa4_limits.h P4::kEdgesMax).  The clean windows here have a row of >= 9 in-edges by construction (the kernel before this
     change flagged them with reason 3) and must be polished, exactly; the noisy ones may still meet another limit."""
     if fill:
         monkeypatch.setenv("RVN_POA4_RING_FILL", str(fill))
